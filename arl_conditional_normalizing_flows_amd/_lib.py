@@ -118,6 +118,13 @@ def load(path: os.PathLike | str | None = None):
     if not p.exists():
         raise CnfError(f'{p} is missing: build it with `python -m arl_conditional_normalizing_flows_amd._build` '
                        f'(hipcc --offload-arch=gfx950). There is no CPU fallback.')
+    # torch's wheel carries its own HIP / HSA runtime. Loaded after this library, it is a second
+    # runtime in the process next to the system one this library resolved, and the library's calls
+    # then find no device; loaded first, its libamdhip64 satisfies this library's dependency too.
+    try:
+        import torch  # noqa: F401
+    except ImportError:   # a caller without torch: the system runtime is the only one
+        pass
     lib = C.CDLL(str(p))
     for name, res, args in _SIGS:
         fn = getattr(lib, name)

@@ -2,6 +2,7 @@
 """Benchmark: images/sec of fwd + log-det (+ NLL sums) of the conditional RealNVP hot path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--global-batch G]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +11,17 @@ synthetic inputs already resident in HBM; with N>1 every rank processes its own 
 (weak scaling, BASELINE configs[1] batch 64 per GPU; --global-batch G instead shards a fixed
 global batch of G images: strong scaling, BASELINE configs[3]/[4]) and the 4 NLL sums are
 all-reduced (the path's only exchange step, one RCCL all-reduce of 5 fp32: the 4 sums + the image
-count). value = images processed by all ranks / max-over-ranks wall time of the K timed steps.
+count). value = images processed by all ranks / max-over-ranks wall time of the K timed steps;
+ms_per_step = that wall time / K.
 
-Extra fields of the JSON line (rank 0):
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given (DIR/<name>.npy, float32: what a caller of the timed path receives;
+inputs and weights are seeded, so two builds can be compared output for output) and prints the
+result line. Everything else the benchmark measures runs only with --full.
+
+Extra fields of the JSON line (rank 0). roofline, step_ms_median, serving and cpu_baseline (with
+bits_per_dim_ref) take runs of their own: they need --full and are null in a plain run, where
+step_roofline's step_ms is ms_per_step:
   roofline        the dominant kernel (largest GPU time per step, by kernel symbol): algorithmic
                   FLOPs or bytes per launch / its average duration measured IN THE STREAM (an eager
                   forward with a HIP event pair around every launch, the queue pre-filled so the
@@ -24,6 +33,8 @@ Extra fields of the JSON line (rank 0):
                   oracle's on the same batch and weights (computed in the CPU leg).
   step_ms_median  median of per-step HIP-event times over >= 100 extra graph replays (BASELINE.md's
                   protocol); `value` / `ms_per_step` are the K-step wall-clock means.
+  serving         throughput with --inflight batches in flight (measured before the timed steps).
+  cpu_baseline    the torch-CPU restatement timed on this host (N=1).
 """
 from __future__ import annotations
 
@@ -62,6 +73,28 @@ def synth(cfg, B, seed, noise_alpha=0.98):
     if cfg.data == 'class':
         return class_batch(B, H, W, cfg.x_d, seed=seed, noise_alpha=noise_alpha)
     return sr_batch(B, H, W, cfg.x_d, cfg.sr_pow, seed=seed, noise_alpha=noise_alpha)
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # of array data: under 64 MB with the .npy headers, whichever MB is meant
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: write {name: tensor or array} as DIR/<name>.npy (float32; ranks > 0 append
+    _rank<r> to the name), at most DUMP_BUDGET_BYTES in all: when the whole set is larger, an array
+    over its equal share of the budget is written as a fixed seeded sample of its flattened elements
+    (same indices every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * max(len(arrays), 1))
+    fits = 4 * sum(int(a.numel() if isinstance(a, torch.Tensor) else np.size(a)) for a in arrays.values()) \
+        <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, np.float32)
+        if not fits and a.size > share:
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (f'_rank{rank}' if rank else '') + '.npy'), a)
 
 
 def kernel_symbol(name):
@@ -369,6 +402,11 @@ def train_bench(args, cfg, flow, xy, B, G, world, rank, dist, dev, scaling):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
+    if args.dump_outputs:
+        # what train_step hands back (the tracker means after the last step) and the weights it left
+        arrays = {k: v.reshape(1) for k, v in logs.items()}
+        arrays['params'] = flow.params
+        dump_outputs(args.dump_outputs, arrays, rank)
     if rank == 0:
         fl_img, _by, _n = algorithmic_per_image(flow, B)
         ms = el / args.steps * 1e3
@@ -387,7 +425,7 @@ def train_bench(args, cfg, flow, xy, B, G, world, rank, dist, dev, scaling):
                             'weight gradients', 'traffic': None,
                 'kernel_stats': os.path.relpath(stats[-1], ROOT) if stats else None}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_train(cfg, flow, xy.cpu().numpy(), B)
         out = {'metric': f'images/sec NLL train step (fwd + bwd + Adam), {cfg.name}',
                'value': round(G * args.steps / el, 2), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
@@ -501,8 +539,15 @@ def main():
     ap.add_argument('--logit', type=float, default=0.0, metavar='A',
                     help='with --noise: the logit preprocess (preprocess_dataset_class(LOGITS=True, a=A), '
                          'conv_cINN_base_functions.py:174-231) on the x channels first, fused likewise')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the last step\'s outputs (what a caller of the timed path '
+                         'receives) as DIR/<name>.npy, float32, at most 64 MB in all')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline figure: serving (--inflight), step_ms_median, '
+                         'the per-kernel / roofline pass and the CPU baseline (each with its own --no-* / '
+                         '--inflight switch); a plain run times the steps and prints the result line only')
     ap.add_argument('--inflight', type=int, default=2,
-                    help='also measure serving throughput with this many batches (of the same size) in flight on '
+                    help='with --full: also measure serving throughput with this many batches (of the same size) in flight on '
                          'as many HIP streams, each its own captured step (reported as "serving"; `value` is one '
                          'batch in flight); 1: skip')
     ap.add_argument('--no-graph', action='store_true')
@@ -602,7 +647,7 @@ def main():
             print(f'# rank {rank}: {msg}', file=sys.stderr, flush=True)
 
     serving = None
-    if world == 1 and not inverse and args.inflight > 1:
+    if args.full and world == 1 and not inverse and args.inflight > 1:
         # first, on a fresh runtime: after hipExtLaunchKernelGGL with events (measure_in_stream), or
         # once the step graph has run on the default stream, the runtime serialises the lanes'
         # streams (measured in profiles/diag/diag_serving.py: 59.1k -> 43.3k images/s)
@@ -665,6 +710,17 @@ def main():
     ms = el / args.steps * 1e3
     total_imgs = G * args.steps
     value = total_imgs / el
+    if args.dump_outputs:
+        # the last timed step's outputs, before any further pass touches the buffers
+        if inverse:
+            arrays = {'x': x_out}
+        else:
+            arrays = {'zy': zy, 'logdet': ld, 'nll_per_image': per, 'nll_sums': sums}
+            if noisy:
+                arrays['x_noisy'] = xn
+            if dist is not None:
+                arrays['nll_sums_allreduced'] = red
+        dump_outputs(args.dump_outputs, arrays, rank)
 
     # results of the timed steps
     ld_mean = ld.mean().item() if not inverse else None
@@ -674,7 +730,7 @@ def main():
     if rank == 0:
         # per-step times for the median (BASELINE.md protocol): local work only, rank 0
         st_ms = []
-        if graph is not None:
+        if args.full and graph is not None:
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
             for a, b in evs:
                 a.record()
@@ -685,7 +741,7 @@ def main():
         roof = None
         step_roof = None
         fl_img, by_img, n_ln = algorithmic_per_image(flow, B)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             launches = measure_in_stream(flow, local_step)
             roof, per_k = roofline_for(launches)
             tot = sum(d['ms'] for d in per_k.values())
@@ -703,7 +759,7 @@ def main():
                      'achieved_tflops': round(fl_img * B / (step_ms / 1e3) / 1e12, 3),
                      'achieved_gbs': round(by_img * B / (step_ms / 1e3) / 1e9, 1)}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = (cpu_baseline_inverse(cfg, flow, zy_in.cpu().numpy(), B) if inverse
                    else cpu_baseline(cfg, flow, xn.cpu().numpy() if noisy else xy_np, B))
         H, W, _ = cfg.io_shape
