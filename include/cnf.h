@@ -13,6 +13,15 @@
  *   - The caller allocates ALL device memory (params, activations, workspace);
  *     the library never frees caller pointers. A plan owns only small constant
  *     tables (index maps) that it uploads once, lazily, on first use.
+ *   - A call's outputs are a function of its inputs and the parameters only. The
+ *     library ignores what `workspace` / `train_workspace` hold on entry: they
+ *     need not be zeroed and may hold another call's leftovers or NaN patterns
+ *     (every region is written in a call before that call reads it). Output
+ *     buffers are fully overwritten (the one accumulating argument,
+ *     cnf_coupling_forward's logdet_accum, is named as such). No byte outside the
+ *     buffers given to a call is read for its result or written, and a graph
+ *     replay computes what the eager call does
+ *     (tests/test_state_independence.py).
  *   - Every compute call is asynchronous on the given stream (a hipStream_t passed
  *     as void*; NULL = default stream) and may be captured into a hipGraph.
  *   - Return value: 0 = OK, negative = error class (CNF_E_*); the message is

@@ -322,7 +322,9 @@ def test_deterministic(gpu, name, B):
     """Three forwards of one batch are equal bit for bit. The batches are ones whose k_pw / k_gc
     workgroups loop over several images and whose shape-specialised instantiations run (round 6: a
     constant-cin k_pw build and k_gc staging the next image without a barrier gave run-to-run
-    different outputs at cfg2 B=64 and cfg5 B=2, 2e-2..6e-2 off the oracle)."""
+    different outputs at cfg2 B=64 and cfg5 B=2, 2e-2..6e-2 off the oracle). The three runs share one
+    cached workspace, so runs 2 and 3 see run 1's own leftovers: first-run and stale-data effects are
+    covered by tests/test_state_independence.py."""
     flow, ora, P, xy = _setup(name, B)
     x = torch.from_numpy(xy).to(gpu)
     runs = [flow(x, 1, per_image_logdet=True) for _ in range(3)]
