@@ -44,6 +44,11 @@ struct Options {
     // TRAIN_SCHED bits: 1 weight gradients on the chain streams, 2 recompute the streamed activations
     // (no saves), 4 enqueue net A's chain before net b's (no interleaving)
     int train_sched = 0;
+    // SCHEDULE_CHECK: 1 = cnf_plan_create dry-runs the forward / inverse schedule and refuses a flow they
+    // cannot run; 0 = the plan tables alone (such a plan fails in its first forward or inverse). Unset (-1):
+    // 1 for CNF_GROUP_REFERENCE, 0 for CNF_GROUP_INTENDED, whose plans of flows with streamed layers
+    // (dense grouped image over the LDS budget) serve host-side table checks; cFlow always asks for 1
+    int schedule_check = -1;
 };
 // parses a debug_options string (null / empty: defaults); throws std::invalid_argument on an unknown
 // name or a malformed value (cnf_runtime.cpp)

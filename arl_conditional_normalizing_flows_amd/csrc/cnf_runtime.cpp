@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 
@@ -77,7 +78,7 @@ Options parse_options(const char* s) {
                                    {"PW", &Options::pw},                   {"GENERIC", &Options::generic},
                                    {"LAYOUT", &Options::layout},           {"FUSE_COUPLING", &Options::fuse_coupling},
                                    {"LDS_BWD", &Options::lds_bwd},         {"TRAIN_ALT", &Options::train_alt},
-                                   {"TRAIN_SCHED", &Options::train_sched}};
+                                   {"TRAIN_SCHED", &Options::train_sched}, {"SCHEDULE_CHECK", &Options::schedule_check}};
     std::string str(s);
     size_t pos = 0;
     while (pos < str.size()) {
@@ -1161,6 +1162,11 @@ static void check_launch() { hip_check(hipGetLastError(), "kernel launch"); }
 
 using namespace cnf;
 
+// host-only dry run of the B-image forward (direction +1) or inverse (-1) schedule: nothing is launched or
+// dereferenced, the launch names land in p.dry_launches; throws what the real call would throw before its
+// first launch (defined after the schedules, below)
+static void dry_run(Plan& p, int B, int direction);
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -1173,7 +1179,8 @@ int cnf_plan_create(const cnf_flow_desc* desc, cnf_plan** out) {
     if (!out) return fail(CNF_E_INVALID, "null out");
     *out = nullptr;
     CNF_TRY
-    Plan* p = build_plan(desc);   // (parses desc->debug_options into p->opts)
+    std::unique_ptr<Plan> owner(build_plan(desc));   // (the reference's asserts; parses desc->debug_options into p->opts)
+    Plan* p = owner.get();
     OptScope os(&p->opts);
     p->use_pw = p->tap_pw = p->opts.pw != 0;
     // validate tiling / LDS budget for every layer up-front
@@ -1184,7 +1191,19 @@ int cnf_plan_create(const cnf_flow_desc* desc, cnf_plan** out) {
         LdsBwdArgs a;
         c.lds_bwd = lds_bwd && c.use_lds && ldsbwd_setup(*p, c, a) > 0;
     }
-    *out = new cnf_plan{p};
+    // a created plan can be scheduled: what the forward or the inverse schedule cannot run (a streamed conv
+    // with more than 64 output channels, a tile over the LDS budget, ...) fails here, like the reference's
+    // asserts, with the schedule's own message -- not on the first batch. One image, and a batch whose
+    // image-looping launches are sized differently. (Debug option SCHEDULE_CHECK=0: plan tables only, the
+    // default for group_mode 'intended' through the C ABI; cFlow asks for the check in either mode.)
+    const int sc = p->opts.schedule_check;
+    if (sc < 0 ? desc->group_mode == CNF_GROUP_REFERENCE : sc != 0)
+        for (int B : {1, 3})
+            for (int dir : {+1, -1}) dry_run(*p, B, dir);
+    p->dry_launches.clear();
+    p->pw_shapes.clear();
+    p->gc_launch.clear();
+    *out = new cnf_plan{owner.release()};
     return CNF_OK;
     CNF_CATCH
 }
@@ -1631,6 +1650,25 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
     if (!p.dry) check_launch();
 }
 
+static void dry_run(Plan& p, int B, int direction) {
+    p.dry = true;
+    p.dry_launches.clear();
+    char* fake = reinterpret_cast<char*>(uintptr_t(1) << 40);   // never dereferenced
+    const float* f = reinterpret_cast<const float*>(fake);
+    float* g = reinterpret_cast<float*>(fake + (1 << 20));        // a distinct output address
+    try {
+        if (direction > 0)
+            flow_forward(p, f, f, f, g, g, fake, B, nullptr, false);
+        else
+            flow_inverse(p, f, f, f, g, fake, B, nullptr);
+    } catch (...) {
+        p.dry = false;
+        throw;
+    }
+    p.dry = false;
+    p.recorded.clear();
+}
+
 extern "C" {
 
 int cnf_coupling_forward(cnf_plan* plan, int layer, const float* params, const float* aux, const float* u, float* v,
@@ -1867,22 +1905,7 @@ int cnf_debug_schedule(cnf_plan* plan, int B, int direction, char* out, int cap)
     if (!plan || !out || cap <= 0 || B <= 0 || (direction != 1 && direction != -1)) return -1;
     Plan& p = *plan->p;
     CNF_TRY
-    p.dry = true;
-    p.dry_launches.clear();
-    char* fake = reinterpret_cast<char*>(uintptr_t(1) << 40);   // never dereferenced
-    const float* f = reinterpret_cast<const float*>(fake);
-    float* g = reinterpret_cast<float*>(fake + (1 << 20));        // a distinct output address
-    try {
-        if (direction > 0)
-            flow_forward(p, f, f, f, g, g, fake, B, nullptr, false);
-        else
-            flow_inverse(p, f, f, f, g, fake, B, nullptr);
-    } catch (...) {
-        p.dry = false;
-        throw;
-    }
-    p.dry = false;
-    p.recorded.clear();
+    dry_run(p, B, direction);
     std::string s;
     for (const std::string& n : p.dry_launches) s += n + "\n";
     if ((int)s.size() + 1 > cap) return -1;

@@ -322,7 +322,12 @@ class cFlow:
         if isinstance(debug_options, dict):
             debug_options = ','.join(f'{k}={int(v)}' for k, v in debug_options.items())
         self.debug_options = debug_options or ''
-        self._opts_buf = C.create_string_buffer(self.debug_options.encode())
+        # a flow the kernels cannot run fails here, like the reference's asserts, in either group mode
+        # (through the C ABI an 'intended' plan is not dry-run by default: include/cnf.h)
+        opts = self.debug_options
+        if 'SCHEDULE_CHECK' not in opts:
+            opts = (opts + ',' if opts else '') + 'SCHEDULE_CHECK=1'
+        self._opts_buf = C.create_string_buffer(opts.encode())
         desc.debug_options = C.cast(self._opts_buf, C.c_char_p)
         plan = C.c_void_p()
         check(lib.cnf_plan_create(C.byref(desc), C.byref(plan)), 'cFlow')

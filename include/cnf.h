@@ -67,12 +67,17 @@ typedef struct cnf_flow_desc {
     const int* cardinality_list;          /* [num_blocks] */
     float lambda_y;                       /* default 100 */
     int ksize;                            /* default 3 (only 3 is implemented on GPU) */
+    /* Limits of the kernels beyond the reference's asserts, checked at cnf_plan_create (CNF_E_INVALID,
+     * "conv with more than 64 output channels"): no convolution inside an s,t network has more than 64
+     * output channels, i.e. every num_kernels_list entry is at most 64 (k_net_lds holds at most 64, and
+     * the streamed kernels tile 64 output columns; only conv_out is split into 64-channel chunks, so
+     * dc2 may exceed 64). Compressed images are at most 128 pixels wide. */
     int layer_norm;                       /* LAYER_NORM, default 1 */
     int dilations;                        /* DILATIONS, default 1 */
     int group_mode;                       /* CNF_GROUP_* (default REFERENCE) */
     /* Debug options, NULL or "" for the defaults (what is benchmarked): "NAME=V[,NAME=V...]" selecting
      * the alternative code paths the parity tests compare against — NETLDS, GC, PW, GENERIC, LAYOUT,
-     * FUSE_COUPLING, LDS_BWD, TRAIN_ALT, TRAIN_SCHED (meanings: csrc/cnf_kernels.h Options). Parsed at
+     * FUSE_COUPLING, LDS_BWD, TRAIN_ALT, TRAIN_SCHED, SCHEDULE_CHECK (meanings: csrc/cnf_kernels.h Options). Parsed at
      * cnf_plan_create (unknown name: CNF_E_INVALID); the string is not kept. Without a GENERIC entry, a
      * flow on images of 64 x 64 and above runs the generic k_pw / k_gc kernels (GENERIC=6; the
      * shape-specialised ones showed intermittent differences there). The library reads no
@@ -98,7 +103,13 @@ typedef struct cnf_layer_info {
 } cnf_layer_info;
 
 /* Plan = cFlow.__init__ (:1431-1695): asserts, scale schedule, dilation
- * schedule, layer list, canonical parameter table. Host-only, no GPU work. */
+ * schedule, layer list, canonical parameter table. Host-only, no GPU work.
+ * A created plan can be scheduled: after the reference's asserts, the forward and
+ * the inverse schedule are dry-run on the host, and a configuration they cannot
+ * run is refused here with the schedule's message, not on the first batch
+ * (debug option SCHEDULE_CHECK=0: the plan tables alone, for host-side checks;
+ * that is the default for CNF_GROUP_INTENDED, SCHEDULE_CHECK=1 asks for the
+ * check there too, as cFlow does). */
 int cnf_plan_create(const cnf_flow_desc* desc, cnf_plan** out);
 void cnf_plan_destroy(cnf_plan* plan);
 

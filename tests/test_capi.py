@@ -32,7 +32,8 @@ def _plan(lib, kw, group_mode=0, options=None):
     arr = lambda v: (C.c_int * len(v))(*v)
     keep = [arr(kw['squeeze_factor_block_list']), arr(kw['ResNeXt_block_list']), arr(kw['num_kernels_list']),
             arr(kw['cardinality_list'])]
-    d = _lib.cnf_flow_desc(*kw['io_shape'], kw['x_d'], len(keep[0]), *keep, 100.0, 3, 1, 1, group_mode,
+    d = _lib.cnf_flow_desc(*kw['io_shape'], kw['x_d'], len(keep[0]), *keep, float(kw.get('lambda_y', 100.0)), 3,
+                           int(kw.get('LAYER_NORM', True)), int(kw.get('DILATIONS', True)), group_mode,
                            options.encode() if options else None)
     p = C.c_void_p()
     rc = lib.cnf_plan_create(C.byref(d), C.byref(p))
@@ -44,6 +45,11 @@ def _plan(lib, kw, group_mode=0, options=None):
 def test_plan_matches_oracle(lib, name, gm):
     kw = PRESETS[name].kwargs()
     kw.pop('group_mode')
+    check_plan_matches_oracle(lib, kw, gm)
+
+
+def check_plan_matches_oracle(lib, kw, gm='reference'):
+    """kw: cFlow constructor arguments without group_mode (LAYER_NORM / DILATIONS are passed on to the plan)."""
     rc, p, keep = _plan(lib, kw, 0 if gm == 'reference' else 1)
     assert rc == 0, lib.cnf_last_error()
     try:
@@ -395,22 +401,25 @@ def test_t2_layout_is_dense_per_producer(lib, name):
     assert (mapped > 0) == (name in ('cfg4', 'cfg5'))
 
 
-def _schedule(lib, name, B, direction):
+def schedule_of_plan(lib, p, B, direction):
+    """launch names of the host-only dry run of the forward (+1) / inverse (-1) of plan p"""
     lib.cnf_debug_schedule.restype = C.c_int
     lib.cnf_debug_schedule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(1 << 16)
+    n = lib.cnf_debug_schedule(p, B, direction, buf, 1 << 16)
+    assert n > 0, lib.cnf_last_error()
+    names = buf.value.decode().split('\n')[:-1]
+    assert len(names) == n
+    return names
+
+
+def _schedule(lib, name, B, direction):
     kw = PRESETS[name].kwargs()
-    lists = [(C.c_int * len(kw[k]))(*kw[k]) for k in ('squeeze_factor_block_list', 'ResNeXt_block_list',
-                                                        'num_kernels_list', 'cardinality_list')]
-    d = _lib.cnf_flow_desc(*kw['io_shape'], kw['x_d'], len(lists[0]), *lists, 100.0, 3, 1, 1, 0)
-    p = C.c_void_p()
-    assert lib.cnf_plan_create(C.byref(d), C.byref(p)) == 0
+    kw.pop('group_mode')
+    rc, p, keep = _plan(lib, kw)
+    assert rc == 0
     try:
-        buf = C.create_string_buffer(1 << 16)
-        n = lib.cnf_debug_schedule(p, B, direction, buf, 1 << 16)
-        assert n > 0, lib.cnf_last_error()
-        names = buf.value.decode().split('\n')[:-1]
-        assert len(names) == n
-        return names
+        return schedule_of_plan(lib, p, B, direction)
     finally:
         lib.cnf_plan_destroy(p)
 

@@ -184,16 +184,30 @@ def test_gradients_match_oracle(gpu, name, B, extra):
     options = extra.pop('_opts', None)
     cfg = PRESETS[name]
     kw = dict(cfg.kwargs(), **extra)
+    xy = _batch(cfg, B, 6)
+    perturb = None
+    if name in PERTURB_CASES:
+        perturb = (PERTURB, PERTURB_SEEDS) if B < 32 else PERTURB_LARGE_B
+    check_gradients(gpu, kw, xy, options, f'{name} {extra}', perturb)
+
+
+def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None):
+    """The HIP gradient of the flow cFlow(**kw) at xy (weights init_params(5)) and its 4 loss terms against
+    float64 autograd, under the module docstring's bar. perturb: None (no perturbation term) or (eps list,
+    seeds per eps). refs: (G_ref, terms_ref, G32) of this kw and xy when the caller has them already."""
+    B = xy.shape[0]
     ora = OracleCFlow(**kw)
     P = ora.init_params(5)
-    xy = _batch(cfg, B, 6)
-    G_ref, terms_ref = oracle_grads(kw, P, xy)
-    G32, _ = oracle_grads(kw, P, xy, torch.float32)
+    if refs is None:
+        G_ref, terms_ref = oracle_grads(kw, P, xy)
+        G32, _ = oracle_grads(kw, P, xy, torch.float32)
+    else:
+        G_ref, terms_ref, G32 = refs
     # float64 gradient's own spread under input perturbations of the fp32 forward's rounding size
     G_spread = {k: np.zeros(np.size(v)) for k, v in G_ref.items()}
-    if name in PERTURB_CASES:
+    if perturb is not None:
         rng = np.random.default_rng(11)
-        eps_list, seeds = (PERTURB, PERTURB_SEEDS) if B < 32 else PERTURB_LARGE_B
+        eps_list, seeds = perturb
         for eps in eps_list:
             for _ in range(seeds):
                 Gp, _ = oracle_grads(kw, P, np.asarray(xy, np.float64) * (1.0 + eps * rng.standard_normal(xy.shape)))
@@ -226,7 +240,7 @@ def test_gradients_match_oracle(gpu, name, B, extra):
         if err > tol:
             bad.append(f'{n}: max|dg| {err:.3e} > tol {tol:.3e} (max|g_ref| {np.max(np.abs(ref)):.3e}, '
                        f'fp32 autograd err {np.max(np.abs(g32 - ref)):.3e})')
-    print(f'{name} {extra} B={B}: worst gradient error / tolerance {worst[0]:.3f} ({worst[1]}), max|g| {gmax:.3e}')
+    print(f'{label} B={B}: worst gradient error / tolerance {worst[0]:.3f} ({worst[1]}), max|g| {gmax:.3e}')
     assert not bad, '\n'.join(bad)
 
 
