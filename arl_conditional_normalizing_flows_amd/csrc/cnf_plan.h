@@ -304,4 +304,68 @@ void coupling_layer_backward(Plan& p, int ci, const float* params, const float* 
 // builds the plan; throws std::invalid_argument with the reference's assertion text
 Plan* build_plan(const cnf_flow_desc* d);
 
+// ---- cnf_coupling.cpp: one coupling layer as launches -------------------------------------------------
+// row-band tiling of the 3x3 kernels: TH rows per tile, tiles per image, 64 * MR pixels per tile;
+// throws std::invalid_argument for an image wider than a tile
+struct Geo {
+    int TH, tiles, MR;
+};
+Geo conv_geo(int h, int w);
+// log-det partial slots (= k_coupling workgroups) per image: one per 64 compressed pixels, so the
+// largest layers run one element per thread (latency-bound otherwise)
+int ld_parts_for(int npx);
+// LN-partial slots per image written by a k_conv3 problem, a k_pw / k_conv1 problem, a k_gc group (one
+// per wave: GC_NW_MAX bounds every instantiation) and, as the bound over the launch paths its branches
+// can take, by the whole grouped stage of a coupling
+int ln_slots_conv3(int h, int w);
+int ln_slots_pw(int h, int w);
+int ln_slots_conv1(int h, int w);
+int ln_slots_gc(const Coupling::GcGroup& g, int waves = GC_NW_MAX);
+int ln_slots_grouped(const Coupling& c);
+
+// one call's view of the plan, the caller's memory and the stream
+struct Exec {
+    Plan& p;
+    const float* params;
+    const float* aux;
+    char* ws;
+    WsLayout L;
+    int B;
+    hipStream_t st;
+
+    template <class T>
+    T* at(size_t off) const {
+        return reinterpret_cast<T*>(ws + off);
+    }
+    // issues fn on the stream and records it for relaunch / timing (dry runs: the name only)
+    void record(const std::string& name, double flops, double bytes, std::function<void(void*)> fn);
+};
+
+// launch-independent part of the k_gc launch over group gg of coupling c (lnst: GcShape::lnst)
+GcShape gc_shape(const Coupling& c, const Coupling::GcGroup& gg, int lnst);
+// k_net_lds geometry for coupling c; returns the LDS bytes (0 if the layer cannot use it)
+size_t netlds_setup(const Plan& p, const Coupling& c, NetLdsArgs& a);
+
+struct CouplingOpts {
+    // the previous layer's deferred coupling, applied by this layer's k_net_lds (LDS layers only)
+    const CoupPend* pend = nullptr;
+    // leave this layer's own coupling pending (no k_coupling launch) and describe it in *out_pend for the
+    // next launch (the caller allows it only when that is a k_net_lds of the same direction or the maps)
+    bool defer = false;
+    CoupPend* out_pend = nullptr;
+    // training forward of a layer with the fused LDS backward: k_net_lds also writes the raw activations
+    // and LN statistics to save (LdsSave blocks)
+    float* save = nullptr;
+    // training forward: the raw s / t outputs go here instead of the workspace
+    float* const* so_save = nullptr;
+    // training forward of a streamed layer: its activations and LN statistics are saved
+    const TrainLayout::StreamSave* ss = nullptr;
+    // first coupling of cnf_flow_forward_noise, k_net_lds layers only: u is the noisy-input buffer,
+    // written by this layer's k_net_lds from nz->src (the fused gather)
+    const InputPrepArgs* nz = nullptr;
+};
+// One coupling layer: u -> v. dir=+1 forward (ld_part may collect the sum of s), dir=-1 inverse.
+void run_coupling(Exec& E, const Coupling& c, const float* u, float* v, double* ld_part, int dir,
+                  const CouplingOpts& o = CouplingOpts{});
+
 }  // namespace cnf

@@ -1,8 +1,8 @@
 // cnf_runtime.cpp — plan execution and the C ABI of libcnf_hip.so (include/cnf.h).
 //
 // Executes the layer schedule of cFlow.call (conv_cINN_make_model.py:1723-1798) as a fixed
-// sequence of k_conv / k_coupling / map launches on the caller's stream. All memory is the
-// caller's (params, aux, workspace); the plan owns only its index tables.
+// sequence of coupling layers (cnf_coupling.cpp) and map launches on the caller's stream. All memory
+// is the caller's (params, aux, workspace); the plan owns only its index tables.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -120,47 +120,6 @@ LaunchTiming& launch_timing() {
     return t;
 }
 
-// ----------------------------------------------------------------------------------------------
-// geometry
-// ----------------------------------------------------------------------------------------------
-struct Geo {
-    int TH, tiles, MR;
-};
-
-static Geo conv_geo(int h, int w) {
-    Geo g;
-    g.MR = (h * w >= 1024) ? 2 : 1;
-    const int pt = 64 * g.MR;
-    if (w > pt) throw std::invalid_argument("image width too large for the row-band tiling (w > 128)");
-    g.TH = std::min(h, std::max(1, pt / w));
-    g.tiles = (h + g.TH - 1) / g.TH;
-    return g;
-}
-
-static int lds_stride(int cin) {  // pixel stride in floats, == 2 (mod 4): conflict-free A reads
-    int s = std::max(cin, 2);
-    while (s % 4 != 2) s++;
-    return s;
-}
-
-struct ConvGeom1 {
-    int MR, P, tiles;
-};
-static ConvGeom1 conv1_geo(int h, int w) {
-    ConvGeom1 g;
-    const int hw = h * w;
-    g.MR = (hw >= 1024) ? 2 : 1;
-    g.P = 64 * g.MR;
-    g.tiles = (hw + g.P - 1) / g.P;
-    return g;
-}
-
-// log-det partial slots (= k_coupling workgroups) per image: one per 64 compressed pixels, so the
-// largest layers run one element per thread (latency-bound otherwise)
-static int ld_parts_for(int npx) { return std::max(1, std::min(16, (npx + 63) / 64)); }
-
-static uint32_t udiv_magic_host(uint32_t d) { return d <= 1 ? 0u : 0xFFFFFFFFu / d + 1u; }   // cnf_device.h udiv
-
 WsLayout Plan::layout(int B) const {
     WsLayout L;
     int64_t n_uv = (int64_t)desc.io_h * desc.io_w * desc.io_d;
@@ -172,21 +131,10 @@ WsLayout Plan::layout(int B) const {
         n_y = std::max<int64_t>(n_y, npx * c.nk);
         n_t2 = std::max<int64_t>(n_t2, npx * c.gc);
         n_so = std::max<int64_t>(n_so, npx * c.dc2);
-        Geo g = conv_geo(c.hc, c.wc);
-        parts = std::max(parts, 4 * g.tiles * (int)c.br.size());   // 4 waves per workgroup
-        parts = std::max(parts, 4 * conv1_geo(c.hc, c.wc).tiles);
-        parts = std::max(parts, 4 * ((c.hc * c.wc + 63) / 64));   // k_pw
-        parts = std::max(parts, (int)c.br.size() * std::max(4 * g.tiles, 4 * ((c.hc * c.wc + 63) / 64)));   // mixed branches
-        if (c.gc_fused) {   // k_gc groups' slots, then the tap-mode / k_conv<3> branches' after them
-            int gp = 0, ing = 0;
-            for (const auto& gg : c.gcg) {
-                gp += GC_NW_MAX * gg.tiles();
-                ing += (int)gg.br.size();
-            }
-            const int rest = (int)c.br.size() - ing;
-            gp += rest * std::max(4 * g.tiles, 4 * ((c.hc * c.wc + 63) / 64));
-            parts = std::max(parts, gp);
-        }
+        // LN partial slots: the 1x1 launches as either kernel, and the grouped stage (whose bound also
+        // covers a k_conv3 problem of conv_in)
+        parts = std::max(parts, std::max(ln_slots_pw(c.hc, c.wc), ln_slots_conv1(c.hc, c.wc)));
+        parts = std::max(parts, ln_slots_grouped(c));
         ldp = std::max(ldp, ld_parts_for((int)npx));
     }
     L.n_uv = n_uv;
@@ -220,912 +168,6 @@ WsLayout Plan::layout(int B) const {
     L.ld = take(std::max<size_t>(1, couplings.size()) * Bz * ldp * 8);
     L.total = off;
     return L;
-}
-
-// ----------------------------------------------------------------------------------------------
-// launch helpers
-// ----------------------------------------------------------------------------------------------
-struct Exec {
-    Plan& p;
-    const float* params;
-    const float* aux;
-    char* ws;
-    WsLayout L;
-    int B;
-    hipStream_t st;
-
-    template <class T>
-    T* at(size_t off) const {
-        return reinterpret_cast<T*>(ws + off);
-    }
-
-    void record(const std::string& name, double flops, double bytes, std::function<void(void*)> fn) {
-        if (p.dry) {
-            p.dry_launches.push_back(name);
-            return;
-        }
-        const size_t k = p.recorded.size();
-        const bool timed = p.timing && p.record && name.rfind("k_", 0) == 0;   // kernels only (not copies)
-        if (timed) {
-            while (p.ev.size() < 2 * (k + 1)) {
-                hipEvent_t e;
-                if (hipEventCreate(&e) != hipSuccess) throw std::runtime_error("hipEventCreate");
-                p.ev.push_back(e);
-            }
-            launch_timing() = LaunchTiming{p.ev[2 * k], p.ev[2 * k + 1]};
-        }
-        try {
-            fn(st);
-        } catch (...) {
-            launch_timing() = LaunchTiming{};
-            throw;
-        }
-        // timed only when exactly one kernel wrote the pair (a launch helper may issue none)
-        const bool wrote = timed && launch_timing().used == 1;
-        launch_timing() = LaunchTiming{};
-        if (p.record) {
-            Recorded r;
-            r.name = name;
-            r.flops = flops;
-            r.bytes = bytes;
-            r.relaunch = std::move(fn);
-            r.timed = wrote;
-            p.recorded.push_back(std::move(r));
-        }
-    }
-};
-
-// LN statistics slab of one tensor: per-wave partials [B][st_parts][LNP] of which the last producer
-// wrote the first nparts (see ConvProb)
-struct Slab {
-    float* part = nullptr;
-    int nparts = 0;
-};
-
-struct ProbSpec {
-    const float* in;
-    int in_cs, in_off, cin;
-    Slab in_st;               // input LN partials (.part == null: no LN)
-    const float* gamma;
-    const float* beta;
-    int act;
-    const float* wt;
-    const float* bias;
-    float* out;
-    int out_cs, out_off, cout;
-    const float* res;
-    Slab out_st;              // .part == null: no output statistics
-    int out_part_base;        // first partial slot of this problem
-    int dil;
-    float* out2 = nullptr;    // k_pw only: every output channel also to a plain [B][HW][cout] tensor
-};
-
-static const char* role_name(int r) {
-    switch (r) {
-        case ROLE_CONV_IN: return "conv_in";
-        case ROLE_CONV_A: return "conv_a";
-        case ROLE_GC: return "gc";
-        case ROLE_CONV_B: return "conv_b";
-        default: return "conv_out";
-    }
-}
-
-static uint32_t magic_for(int d, int64_t xmax) {
-    // x / d == umulhi(x, ceil(2^32 / d)) exactly while x * d * d < 2^32 (error term x*e/2^32 < 1/d)
-    if (d <= 1) return 0;
-    if ((double)xmax * d * d >= 4294967296.0) throw std::invalid_argument("magic division out of range");
-    return (uint32_t)((((uint64_t)1 << 32) + (uint64_t)d - 1) / (uint64_t)d);
-}
-
-// tap-mode source of a k_pw launch (streamed conv_in): the probs' `in` is the raw layer input u, the
-// A operand the 3x3 im2col row over the mask-compressed half (K = 9 * dc), gathered in the kernel
-struct TapSrc {
-    int mask, W, D, dc, img;   // mask, full-res width / depth, channels per tap, floats per image of u
-    int dil = 1, off = 0;      // mask < 0: plain NHWC source (D channels), taps from channel off, dilation
-};
-
-// returns the LN-partial slots per image each problem writes (4 per workgroup tile)
-static int conv_launch(Exec& E, int ks, int role, int h, int w, const std::vector<ProbSpec>& probs,
-                       uint64_t store_mask = ~0ull, const TapSrc* tap = nullptr, const int* st_map = nullptr,
-                       const int* in_map = nullptr, bool* dual_done = nullptr) {
-    const bool st_compact = st_map != nullptr;
-    if (probs.empty()) return 0;
-    if ((int)probs.size() > MAXPROB) throw std::invalid_argument("too many problems in one conv launch");
-    ConvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.H = h;
-    a.W = w;
-    a.nprob = (int)probs.size();
-    a.B = E.B;
-    Geo g{0, 0, 0};
-    ConvGeom1 g1{0, 0, 0};
-    if (ks == 3) {
-        g = conv_geo(h, w);
-        a.TH = g.TH;
-        a.tiles_per_img = g.tiles;
-    } else {
-        g1 = conv1_geo(h, w);
-        a.P = g1.P;
-        a.tiles_per_img = g1.tiles;
-    }
-    size_t lds = 0;
-    double flops = 0, bytes = 0;
-    const double HWB = (double)h * w * E.B;
-    bool vec = true;
-    int pw_nr = 0, pw_gm = 0;
-    for (size_t i = 0; i < probs.size(); i++) {
-        const ProbSpec& s = probs[i];
-        ConvProb& q = a.p[i];
-        q.in = s.in;
-        q.in_part = s.in_st.part;
-        q.in_nparts = s.in_st.nparts;
-        q.gamma = s.gamma;
-        q.beta = s.beta;
-        q.wt = s.wt;
-        q.bias = s.bias;
-        q.res = s.res;
-        q.out = s.out;
-        q.out_part = s.out_st.part;
-        q.in_cs = s.in_cs;
-        q.in_off = s.in_off;
-        q.cin = s.cin;
-        q.out_cs = s.out_cs;
-        q.out_off = s.out_off;
-        q.cout = s.cout;
-        q.part_stride = E.L.st_parts;
-        q.out_part_base = s.out_part_base;
-        q.dil = s.dil;
-        q.act = s.act;
-        q.st_mask_lo = (uint32_t)(store_mask & 0xffffffffull);
-        q.st_mask_hi = (uint32_t)(store_mask >> 32);
-        q.st_compact = st_compact ? 1 : 0;
-        q.st_map = st_map;
-        q.in_mapped = in_map != nullptr ? 1 : 0;
-        q.in_map = in_map;
-        q.out2 = s.out2;
-        if (in_map != nullptr && (ks != 1 || tap != nullptr || s.in_off != 0 || s.cin % 4 != 0))
-            throw std::logic_error("mapped input: plain k_pw over whole quads only");
-        if (st_compact && (s.res != nullptr || s.cout > 64)) throw std::logic_error("mapped stores: no residual, <= 64 outputs");
-        if (s.cout > 64) throw std::invalid_argument("conv with more than 64 output channels");
-        const int K = ks * ks * s.cin;
-        q.nr = (s.cout + 15) / 16;
-        size_t off = 128;
-        if (ks == 3) {
-            q.S = lds_stride(s.cin);
-            q.Kpad = (K + 3) / 4 * 4;
-            q.NS = 16 * q.nr;
-            if (q.NS % 32 == 0) q.NS += 16;
-            const int d = s.dil;
-            const int WP = w + 2 * d;
-            const int SR = g.TH + 2 * d;
-            const int64_t total = (int64_t)SR * WP * s.cin;
-            q.cin_mag = magic_for(s.cin, total + 256 * 4);
-            q.wp_mag = magic_for(WP, (int64_t)SR * WP + 256 * 4);
-            if (WP == 1) throw std::invalid_argument("degenerate width");
-            size_t lin_f = (size_t)SR * WP * q.S;
-            q.lds_in_off = (int)off;
-            off = align_up(off + lin_f * 4, 16);
-            q.lds_w_off = (int)off;
-            off = align_up(off + (size_t)q.Kpad * q.NS * 4, 16);
-            q.lds_k_off = (int)off;
-            off = align_up(off + (size_t)q.Kpad * 4, 16);
-        } else {
-            const int G = (s.cin + 15) / 16;
-            if (off < 512) off = 512;   // k_pw keeps its per-image LN table at bytes [256, 384)
-            q.lds_w_off = (int)off;
-            // k_pw stages the weights as the three bf16 planes of 32-deep K steps (1 KiB per plane, step and
-            // 16-column block); k_conv1 reads the fp32 image, G x 16 x 16 x nr floats, which fits in it
-            const size_t wx6 = (size_t)((s.cin + 31) / 32) * 3 * q.nr * 1024;
-            off = align_up(off + std::max(wx6, (size_t)G * 16 * 16 * q.nr * 4), 16);
-            // k_pw loads every channel quad the input window starts with 16 bytes at a time: a window
-            // that is not quad-aligned (conv_b over the 62- / 30-channel concat of cfg5's grouped
-            // stages) reads past its last channel into the next pixel (or 0 past the image), which
-            // meets zero weight rows (the packed image pads K with zeros)
-            pw_nr = std::max(pw_nr, q.nr);
-            pw_gm = std::max(pw_gm, G);
-        }
-        lds = std::max(lds, off);
-        flops += 2.0 * HWB * K * s.cout;
-        // output bytes count only the stored channels (conv_a stores just the grouped branches' inputs)
-        const uint64_t cmask = s.cout >= 64 ? ~0ull : ((1ull << s.cout) - 1);
-        const double stored = (double)__builtin_popcountll(store_mask & cmask);
-        bytes += 4.0 * (HWB * (tap ? tap->dc : s.cin) + HWB * (stored + (s.res ? s.cout : 0)) +
-                        (s.in_st.part ? 2.0 * h * w * (tap ? tap->dc : s.cin) : 0.0) +
-                        (double)K * s.cout + s.cout);
-    }
-    if (lds > 160 * 1024) throw std::invalid_argument("conv tile exceeds the 160 KiB LDS budget");
-    if (ks == 1)   // k_pw stages every problem's weights as pw_nr column blocks: the workgroup's LDS covers them
-        for (int i = 0; i < a.nprob; i++)
-            if ((size_t)a.p[i].lds_w_off + (size_t)((a.p[i].cin + 31) / 32) * 3 * pw_nr * 1024 > lds || a.p[i].nr != pw_nr)
-                throw std::logic_error("k_pw launch: problems of different widths or LDS short of the weight planes");
-    const int ilds = (int)lds;
-    if (pw_gm > 0) pw_gm = pw_gm <= 1 ? 1 : pw_gm <= 2 ? 2 : pw_gm <= 4 ? 4 : pw_gm <= 8 ? 8 : 0;
-    bool ln_uniform = true;
-    for (const ProbSpec& s : probs)
-        ln_uniform = ln_uniform && ((s.in_st.part != nullptr) == (probs[0].in_st.part != nullptr)) &&
-                     ((s.res != nullptr) == (probs[0].res != nullptr));
-    bool fits32 = true;   // k_pw addresses one image per buffer resource with 32-bit byte offsets
-    for (const ProbSpec& s : probs)
-        fits32 = fits32 && (double)h * w * std::max(s.in_cs, s.out_cs) * 4.0 < 2147483648.0 &&
-                 (tap == nullptr || (double)tap->img * 4.0 < 2147483648.0);
-    const bool pw_ok = ks == 1 && vec && pw_gm > 0 && ln_uniform && fits32 && E.p.use_pw;
-    if ((st_compact || in_map != nullptr) && !pw_ok) throw std::logic_error("mapped loads / stores need the k_pw path");
-    if (dual_done != nullptr) *dual_done = pw_ok;   // (the other kernels ignore out2)
-    if (!pw_ok)
-        for (int i = 0; i < a.nprob; i++) a.p[i].out2 = nullptr;
-    if (ks == 3) {
-        const int grid_x = E.B * g.tiles;
-        const int mr = g.MR;
-        std::string name = std::string("k_conv3<") + std::to_string(mr) + "," + role_name(role) + ">";
-        E.record(name, flops, bytes, [mr, role, a, grid_x, ilds](void* st) {
-            launch_conv(3, mr, role, a, grid_x, ilds, (hipStream_t)st);
-        });
-        return 4 * g.tiles;
-    } else if (pw_ok) {
-        // k_pw: 64-pixel tiles (4 waves x 16 pixels), each workgroup looping over ipw images, sized
-        // so the launch is one round of two workgroups per CU (see cnf_stream.hip)
-        const bool resf = probs[0].res != nullptr;
-        const int nw = 4;
-        const int tiles = (h * w + 16 * nw - 1) / (16 * nw);
-        a.tiles_per_img = tiles;
-        for (int i = 0; i < a.nprob; i++) a.p[i].out_part_base = probs[i].out_part_base;
-        const int64_t units = (int64_t)tiles * a.nprob * E.B;
-        const bool lnf = probs[0].in_st.part != nullptr;
-        a.ipw = (int)std::min<int64_t>(16, std::max<int64_t>(1, (units + 511) / 512));
-#ifdef CNF_DIAG   // diagnostics: images per workgroup of the residual (conv_b) / other k_pw launches
-        if (const char* e = std::getenv(resf ? "CNF_PW_IPW_RES" : "CNF_PW_IPW")) a.ipw = std::atoi(e);
-#endif
-        const int grid_x = tiles * ((E.B + a.ipw - 1) / a.ipw);
-        const int nr = pw_nr, gm = pw_gm;
-        const bool tapf = tap != nullptr;
-        if (tap) {
-            a.umask = tap->mask;
-            a.uW = tap->W;
-            a.uD = tap->D;
-            a.udc = tap->dc;
-            a.uimg = tap->img;
-            a.udil = tap->dil;
-            a.uoff = tap->off;
-        }
-        if (E.p.dry) {
-            PwShape sh;
-            if (pw_shape_of(nr, gm, lnf, resf, tapf, a, sh)) {
-                bool seen = false;
-                for (const PwShape& o : E.p.pw_shapes) seen = seen || std::memcmp(&o, &sh, sizeof(sh)) == 0;
-                if (!seen) E.p.pw_shapes.push_back(sh);
-            }
-        }
-        std::string name = std::string("k_pw<") + std::to_string(nr) + "," + std::to_string(gm) + "," +
-                           role_name(role) + ">";
-        E.record(name, flops, bytes, [nr, gm, lnf, resf, tapf, a, grid_x, ilds](void* st) {
-            launch_pw(nr, gm, lnf, resf, tapf, a, grid_x, ilds, (hipStream_t)st);
-        });
-        return nw * tiles;
-    } else {
-        const int grid_x = E.B * g1.tiles;
-        const int mr = g1.MR;
-        std::string name = std::string("k_conv1<") + std::to_string(mr) + "," + (vec ? "vec" : "scalar") + "," +
-                           role_name(role) + ">";
-        E.record(name, flops, bytes, [mr, vec, role, a, grid_x, ilds](void* st) {
-            launch_conv1(mr, vec, role, a, grid_x, ilds, (hipStream_t)st);
-        });
-        return 4 * g1.tiles;
-    }
-}
-
-// tap-decomposed 3x3 (dilation 1, cout <= 7): see k_convtap
-static void convtap_launch(Exec& E, int h, int w, const std::vector<ProbSpec>& probs) {
-    ConvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    Geo g = conv_geo(h, w);
-    a.H = h;
-    a.W = w;
-    a.TH = g.TH;
-    a.tiles_per_img = g.tiles;
-    a.nprob = (int)probs.size();
-    a.B = E.B;
-    const int nband = (g.TH + 2) * w;
-    int mt = (nband + 63) / 64;
-    if (mt == 5) mt = 6;
-    if (mt > 6) throw std::invalid_argument("tap conv band too large");
-    size_t lds = 0;
-    double flops = 0, bytes = 0;
-    const double HWB = (double)h * w * E.B;
-    bool vec = true;
-    int pw_nr = 0, pw_gm = 0;
-    for (size_t i = 0; i < probs.size(); i++) {
-        const ProbSpec& s = probs[i];
-        ConvProb& q = a.p[i];
-        q.in = s.in;
-        q.in_part = s.in_st.part;
-        q.in_nparts = s.in_st.nparts;
-        q.part_stride = E.L.st_parts;
-        q.gamma = s.gamma;
-        q.beta = s.beta;
-        q.wt = s.wt;
-        q.bias = s.bias;
-        q.out = s.out;
-        q.in_cs = s.in_cs;
-        q.in_off = s.in_off;
-        q.cin = s.cin;
-        q.out_cs = s.out_cs;
-        q.out_off = s.out_off;
-        q.cout = s.cout;
-        q.act = s.act;
-        q.dil = 1;
-        q.st_mask_lo = q.st_mask_hi = 0xffffffffu;
-        if (9 * s.cout > 64) throw std::invalid_argument("tap conv needs 9*cout <= 64");
-        q.nr = (9 * s.cout + 15) / 16;
-        const int NSJ = 16 * q.nr;
-        const int G = (s.cin + 15) / 16;
-        size_t off = 128;
-        q.lds_w_off = (int)off;
-        off = align_up(off + (size_t)G * 16 * NSJ * 4, 16);
-        q.lds_in_off = (int)off;
-        off = align_up(off + (size_t)nband * (NSJ + 1) * 4, 16);
-        q.lds_k_off = (int)off;
-        off = align_up(off + (size_t)NSJ * 4, 16);
-        lds = std::max(lds, off);
-        if (s.cin % 4 || s.in_cs % 4 || s.in_off % 4) vec = false;
-        flops += 2.0 * HWB * 9 * s.cin * s.cout;
-        bytes += 4.0 * (HWB * s.cin + HWB * s.cout + (s.in_st.part ? 2.0 * h * w * s.cin : 0.0) + 9.0 * s.cin * s.cout);
-    }
-    if (lds > 160 * 1024) throw std::invalid_argument("tap conv exceeds the LDS budget");
-    const int ilds = (int)lds, grid_x = E.B * g.tiles;
-    std::string name = std::string("k_convtap<") + std::to_string(mt) + (vec ? ",vec" : ",scalar") + ",conv_out>";
-    E.record(name, flops, bytes, [mt, vec, a, grid_x, ilds](void* st) {
-        launch_convtap(mt, vec, a, grid_x, ilds, (hipStream_t)st);
-    });
-}
-
-// k_net_lds geometry for coupling c; returns the LDS bytes (0 if the layer cannot use it)
-static size_t netlds_setup(const Plan& p, const Coupling& c, NetLdsArgs& a) {
-    std::memset(&a, 0, sizeof(a));
-    if ((int)c.br.size() > NETLDS_MAXBR) return 0;
-    for (const Branch& b : c.br)
-        if (b.dil > 16) return 0;
-    const int HW = c.hc * c.wc;
-    a.H = c.H;
-    a.W = c.W;
-    a.D = c.D;
-    a.mask = c.mask;
-    a.hc = c.hc;
-    a.wc = c.wc;
-    a.dc1 = c.dc1;
-    a.dc2 = c.dc2;
-    a.nk = c.nk;
-    a.gc = c.gc;
-    a.R = c.R;
-    a.nbr = (int)c.br.size();
-    a.ln = p.desc.layer_norm;
-    for (int i = 0; i < a.nbr; i++) {
-        a.br_cin_off[i] = c.br[i].cin_off;
-        a.br_cin[i] = c.br[i].cin;
-        a.br_cout[i] = c.br[i].cout;
-        a.br_out_off[i] = c.br[i].out_off;
-        a.br_dil[i] = c.br[i].dil;
-    }
-    {   // disjoint union of the grouped branches' input channel windows (normalised once, in place)
-        std::vector<std::pair<int, int>> iv;
-        for (const Branch& b : c.br) iv.push_back({b.cin_off, b.cin_off + b.cin});
-        std::sort(iv.begin(), iv.end());
-        std::vector<std::pair<int, int>> mg;
-        for (auto& x : iv) {
-            if (!mg.empty() && x.first <= mg.back().second)
-                mg.back().second = std::max(mg.back().second, x.second);
-            else
-                mg.push_back(x);
-        }
-        if ((int)mg.size() > NETLDS_MAXBR) return 0;
-        a.nwin = (int)mg.size();
-        for (int i = 0; i < a.nwin; i++) {
-            a.win_off[i] = mg[i].first;
-            a.win_len[i] = mg[i].second - mg[i].first;
-        }
-    }
-    a.offs_per_net = c.lds_offs_per_net;
-    const NetLdsGeom& g = c.lds;
-    a.sy = g.sy;
-    a.s1 = g.s1;
-    a.s2 = g.s2;
-    a.su = g.su;
-    const NetParams& n0 = c.net[0];
-    auto desc = [](const PackedConv& pc) { return LdsConv{pc.fmt, (int)pc.size, pc.kpad, pc.ns}; };
-    a.ci = desc(n0.ci);
-    a.co = desc(n0.co);
-    if (!n0.rb.empty()) {
-        a.ca = desc(n0.rb[0].ca);
-        a.cb = desc(n0.rb[0].cb);
-        for (int i = 0; i < a.nbr; i++) a.gcv[i] = desc(n0.rb[0].gc[i]);
-    }
-    a.off_y = g.off_y;
-    a.off_t1 = g.off_t1;
-    a.off_t2 = g.off_t2;
-    a.off_w = g.off_w;
-    a.off_k = g.off_k;
-    a.off_ks = g.off_ks;
-    auto nr = [](int cout) { return (cout + 15) / 16; };
-    // the tap-decomposed conv_out runs in chunks of at most two 16-column blocks
-    a.maxnr = std::max(nr(c.nk), c.co_fmt == PK_TAP ? std::min(2, nr(9 * c.dc2)) : nr(c.dc2));
-    for (const Branch& b : c.br) a.maxnr = std::max(a.maxnr, nr(b.cout));
-#ifdef CNF_DIAG
-    if (const char* e = std::getenv("CNF_NETLDS_DUMP")) {   // diagnostics: every shape field, as C
-        if (std::atoi(e)) {
-            const int* w = reinterpret_cast<const int*>(&a.offs_per_net);
-            const int n = (int)((reinterpret_cast<const char*>(&a.zero_bias) - reinterpret_cast<const char*>(w)) / 4);
-            std::fprintf(stderr, "NETSHAPE hc=%d wc=%d mask=%d:", c.hc, c.wc, c.mask);
-            for (int i = 0; i < n; i++) std::fprintf(stderr, " %d", w[i]);
-            const int* w2 = reinterpret_cast<const int*>(&a.off_y);
-            for (int i = 0; i < 7; i++) std::fprintf(stderr, " %d", w2[i]);
-            std::fprintf(stderr, "\n");
-        }
-    }
-    if (const char* e = std::getenv("CNF_NETLDS_VERBOSE"))
-        if (std::atoi(e)) std::fprintf(stderr, "netlds layer hc=%d wc=%d nk=%d dc2=%d co_fmt=%d maxnr=%d\n", c.hc, c.wc,
-                                       c.nk, c.dc2, c.co_fmt, a.maxnr);
-#endif
-    return (size_t)g.bytes;
-}
-
-static double net_flops(const Coupling& c) {
-    const double HW = (double)c.hc * c.wc;
-    double f = 9.0 * c.dc1 * c.nk + 9.0 * c.nk * c.dc2;
-    double rb = (double)c.nk * c.nk + (double)c.gc * c.nk;
-    for (const Branch& b : c.br) rb += 9.0 * b.cin * b.cout;
-    return 2.0 * HW * (f + c.R * rb);
-}
-
-// One coupling layer: u -> v. dir=+1 forward (ld_part may collect Σs), dir=-1 inverse.
-// pend: the previous layer's deferred coupling, applied by this layer's k_net_lds (forward, LDS
-// layers only). defer: leave this layer's own coupling pending (no k_coupling launch) and describe it
-// in *out_pend for the next layer's k_net_lds (the caller allows it only when that layer is an LDS
-// layer of the same forward).
-// save / so_save (training forward of a layer with the fused LDS backward): k_net_lds also writes the
-// raw activations and LN statistics to save (LdsSave blocks) and its s / t outputs to so_save[2]
-// nz (first coupling of cnf_flow_forward_noise, k_net_lds layers only): u is the noisy-input buffer,
-// written by this layer's k_net_lds from nz->src (the fused gather)
-static void run_coupling(Exec& E, const Coupling& c, const float* u, float* v, double* ld_part, int dir,
-                         const CoupPend* pend = nullptr, bool defer = false, CoupPend* out_pend = nullptr,
-                         float* save = nullptr, float* const* so_save = nullptr,
-                         const TrainLayout::StreamSave* ss = nullptr, const InputPrepArgs* nz = nullptr) {
-    const int B = E.B;
-    const WsLayout& L = E.L;
-    const float* P = E.params;
-    const float* X = E.aux;
-    const int nt3 = conv_geo(c.hc, c.wc).tiles;     // LN partials written by a 3x3 launch (per problem)
-    const int nt1 = conv1_geo(c.hc, c.wc).tiles;    // ... by a 1x1 launch
-    const int nbr = (int)c.br.size();
-    const bool ln = E.p.desc.layer_norm != 0;
-    // k_net_lds layers alternate between two s/t sets by coupling index, so a layer applying its
-    // predecessor's deferred coupling never writes the set it reads
-    const bool alt = c.use_lds && (c.index & 1) != 0;
-    float* so0 = so_save ? so_save[0] : E.at<float>(alt ? L.so_alt[0] : L.so[0]);
-    float* so1 = so_save ? so_save[1] : E.at<float>(alt ? L.so_alt[1] : L.so[1]);
-    if (save != nullptr && (!c.use_lds || so_save == nullptr || defer))
-        throw std::logic_error("training save: k_net_lds layers without a deferred law only");
-    if ((pend != nullptr || defer) && !c.use_lds)
-        throw std::logic_error("deferred couplings are only fused into k_net_lds layers");
-    if (pend != nullptr && pend->dir != dir) throw std::logic_error("deferred coupling of the other direction");
-    const float* tap_c[2] = {nullptr, nullptr};   // streamed tap-GEMM conv_out (finished in k_coupling)
-    const float* tap_b[2] = {nullptr, nullptr};
-    NetLdsArgs na;
-    const size_t nlds = c.use_lds ? netlds_setup(E.p, c, na) : 0;
-    if (c.use_lds && nlds == 0) throw std::runtime_error("layer planned for k_net_lds does not fit its LDS budget");
-    if (nlds > 0) {
-        na.u = u;
-        na.so[0] = so0;
-        na.so[1] = so1;
-        na.params = P;
-        na.aux = X;
-        na.offs = E.p.dtab(c.dev_lds_offs);
-        for (int n = 0; n < 2; n++) na.ci_off[n] = E.p.host_table[(size_t)c.dev_lds_offs + (size_t)n * na.offs_per_net];
-        na.zero_bias = X + E.p.aux_zero;
-        if (save != nullptr) {
-            const LdsSave s = LdsSave::of(c.hc * c.wc, c.nk, c.gc, c.R);
-            na.save = save;
-            na.save_img = s.img;
-            na.save_t1 = s.t1;
-            na.save_t2 = s.t2;
-            na.save_st = s.st;
-        }
-        if (nz != nullptr) {
-            if (pend != nullptr || save != nullptr) throw std::logic_error("fused input noise: first inference layer only");
-            na.nz = *nz;
-        }
-        if (pend != nullptr) {
-            // buffer discipline of the deferred law (dry runs carry no real pointers): this layer's
-            // input is the pending layer's output v_k, which must not be the u_k it is computed
-            // from, and this layer's s/t outputs must not overwrite the pending s_pre / t it reads
-            // (LDS layers alternate s/t sets by coupling index)
-            if (!E.p.dry && (pend->v != u || pend->u == u || so0 == pend->s_pre || so0 == pend->t ||
-                             so1 == pend->s_pre || so1 == pend->t))
-                throw std::logic_error("deferred coupling: buffer aliasing (v_k / u_k / s,t sets)");
-            na.pend = *pend;
-            na.pend.comp = pend->mask_c == c.mask && pend->hc == c.hc && pend->wc == c.wc && pend->dc2 == c.dc1 ? 1 : 0;
-        }
-        const int ilds = (int)nlds;
-        const double fl = 2.0 * B * net_flops(c);
-        // algorithmic bytes: u1c in and s/t out per image and net, plus the per-element LN
-        // gamma/beta (only the branch input windows of LN2) and the conv weights once per launch
-        const double HWc = (double)c.hc * c.wc;
-        int win = 0;
-        for (int i = 0; i < na.nwin; i++) win += na.win_len[i];
-        const double ln_floats = ln ? 2.0 * HWc * (c.R * (c.nk + win + c.gc) + c.nk) : 0.0;
-        const double w_floats = net_flops(c) / (2.0 * HWc);
-        const double by = 4.0 * (B * HWc * (c.dc1 + c.dc2) * 2 + 2 * (ln_floats + w_floats));
-        E.record("k_net_lds", fl, by, [na, B, ilds](void* st) { launch_net_lds(na, B, ilds, (hipStream_t)st); });
-    } else {
-    if (nz != nullptr) throw std::logic_error("fused input noise: k_net_lds layers only");
-    float* u1c = E.at<float>(L.u1c);
-    // conv_in straight from u (k_pw tap mode: the mask gather inside the im2col loads) when packed
-    const bool cin_tap = E.p.use_pw && c.net[0].ci_pw.size > 0;
-    if (!cin_tap) {
-        const float* uu = u;
-        E.record("k_gather_u1c", 0, 4.0 * B * c.hc * c.wc * c.dc1 * 2,
-                 [=](void* st) { launch_gather_u1c(uu, u1c, B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, (hipStream_t)st); });
-    }
-    float* y[2] = {E.at<float>(L.y[0]), E.at<float>(L.y[1])};
-    float* t1[2] = {E.at<float>(L.t1[0]), E.at<float>(L.t1[1])};
-    float* t2[2] = {E.at<float>(L.t2[0]), E.at<float>(L.t2[1])};
-    float* so[2] = {E.at<float>(L.so[0]), E.at<float>(L.so[1])};
-    // training forward with saved activations (TrainLayout::StreamSave): y_r and t2_r live in per-block
-    // slices of the save area (conv_b writes y_{r+1} next to its residual y_r instead of in place), conv_a
-    // also stores the full t1_r, and every LN tensor's statistics are folded once into [B][2]
-    if (ss != nullptr && c.t2_mapped) throw std::logic_error("training save: mapped t2 layout");
-    const size_t npx = (size_t)c.hc * c.wc;
-    auto SY = [&](int n, int r) { return E.at<float>(ss->y[n]) + (size_t)r * B * npx * c.nk; };
-    auto ST1 = [&](int n, int r) { return E.at<float>(ss->t1[n]) + (size_t)r * B * npx * c.nk; };
-    auto ST2 = [&](int n, int r) { return E.at<float>(ss->t2[n]) + (size_t)r * B * npx * c.gc; };
-    auto SST = [&](int n, int i) { return E.at<float>(ss->st[n]) + (size_t)i * B * 2; };
-    if (ss != nullptr) {
-        for (int n = 0; n < 2; n++) {
-            y[n] = SY(n, 0);
-            t2[n] = ST2(n, 0);
-        }
-        so[0] = so0;   // (so_save: the save area's raw conv_out)
-        so[1] = so1;
-    }
-    Slab sl[2][3];   // [net][y, t1, t2]
-    for (int n = 0; n < 2; n++)
-        for (int k = 0; k < 3; k++) {
-            sl[n][k].part = E.at<float>(L.st_part[n][k]);
-        }
-    // a producing launch reports the partial slots it wrote per image (set_parts); in_slab hands
-    // that count on to the consumer
-    auto out_slab = [&](int n, int k, int) { return ln ? sl[n][k] : Slab{}; };
-    // more slots than a consumer wave fetches in its prologue (64 x LN_FETCH = 512: the 128x128 layers):
-    // merged once per image by k_ln_merge instead of by every consumer workgroup for each of its images
-    // (the 64x64 layers' slots are folded by the consumers: 70 fewer launches per cfg4 step)
-#ifdef CNF_DIAG_NO_LN_MERGE   // (diagnostic builds: the consumers fold every slot)
-    constexpr int ln_merge_over = 1 << 30;
-#else
-    constexpr int ln_merge_over = 64 * LN_FETCH;
-#endif
-    auto set_parts = [&](int k, int nparts) {
-        if (ln && nparts > ln_merge_over) {
-            float* p0 = sl[0][k].part;
-            float* p1 = sl[1][k].part;
-            const int np = nparts, ps = L.st_parts;
-            E.record("k_ln_merge", 0, 16.0 * B * np * 2 + 32.0 * B,
-                     [=](void* st) { launch_ln_merge(p0, p1, np, ps, B, (hipStream_t)st); });
-            nparts = 1;
-        }
-        for (int n = 0; n < 2; n++) sl[n][k].nparts = nparts;
-    };
-    // training save: the statistics of LN tensor i (see TrainLayout::StreamSave) from slab k's slots, folded
-    // by one k_ln_final per residual block (flush_stats before conv_b overwrites slab 0, and at the end):
-    // the three slabs hold y_r, t1_r and t2_r until then
-    LnFinalSet pend_stats{};
-    pend_stats.part_stride = L.st_parts;
-    auto flush_stats = [&]() {
-        if (pend_stats.count == 0) return;
-        const LnFinalSet fs = pend_stats;
-        double bytes = 0.0;
-        for (int q = 0; q < fs.count; q++) bytes += 16.0 * B * fs.nparts[q] * 2;
-        E.record("k_ln_final", 0, bytes, [=](void* st) { launch_ln_final(fs, B, (hipStream_t)st); });
-        pend_stats.count = 0;
-    };
-    auto save_stats = [&](int k, int i) {
-        if (ss == nullptr || !ln) return;
-        if (pend_stats.count == LNF_MAX) flush_stats();
-        const int q = pend_stats.count++;
-        pend_stats.part[q][0] = sl[0][k].part;
-        pend_stats.part[q][1] = sl[1][k].part;
-        pend_stats.st[q][0] = SST(0, i);
-        pend_stats.st[q][1] = SST(1, i);
-        pend_stats.nparts[q] = sl[0][k].nparts;
-    };
-    auto in_slab = [&](int n, int k) { return ln ? sl[n][k] : Slab{}; };
-    const float* none = nullptr;
-    // LN2 gamma/beta in t1's layout: the aux copies gathered to the compact layout, or the parameters
-    auto ln2g = [&](const RBParams& rb) { return c.t1_compact ? X + rb.ln2c_g : P + rb.ln2g; };
-    auto ln2b = [&](const RBParams& rb) { return c.t1_compact ? X + rb.ln2c_b : P + rb.ln2b; };
-    auto ln3g = [&](const RBParams& rb) { return c.t2_mapped ? X + rb.ln3c_g : P + rb.ln3g; };
-    auto ln3b = [&](const RBParams& rb) { return c.t2_mapped ? X + rb.ln3c_b : P + rb.ln3b; };
-    // device-table maps of the mapped layouts (fake, never dereferenced, in dry runs)
-    auto dmap = [&](int off) -> const int* {
-        return E.p.dtab(off);
-    };
-
-    // conv_in (:1114-1119 / :1159-1164): u1c -> y, both nets in one launch
-    if (cin_tap) {
-        std::vector<ProbSpec> pr;
-        for (int n = 0; n < 2; n++) {
-            const NetParams& np = c.net[n];
-            pr.push_back(ProbSpec{u, 9 * c.dc1, 0, 9 * c.dc1, Slab{}, none, none, 0, X + np.ci_pw.w, X + np.ci_pw.b,
-                                  y[n], c.nk, 0, c.nk, none, out_slab(n, 0, 4 * nt1), 0, 1});
-        }
-        const TapSrc ts{c.mask, c.W, c.D, c.dc1, c.H * c.W * c.D};
-        set_parts(0, conv_launch(E, 1, ROLE_CONV_IN, c.hc, c.wc, pr, ~0ull, &ts));
-    } else {
-        std::vector<ProbSpec> pr;
-        for (int n = 0; n < 2; n++) {
-            const NetParams& np = c.net[n];
-            pr.push_back(ProbSpec{u1c, c.dc1, 0, c.dc1, Slab{}, none, none, 0, X + np.ci.w, X + np.ci.b, y[n], c.nk, 0,
-                                  c.nk, none, out_slab(n, 0, 4 * nt3), 0, 1});
-        }
-        set_parts(0, conv_launch(E, 3, ROLE_CONV_IN, c.hc, c.wc, pr));
-    }
-    save_stats(0, 0);
-    for (int r = 0; r < c.R; r++) {
-        if (ss != nullptr)
-            for (int n = 0; n < 2; n++) t2[n] = ST2(n, r);
-        // conv_a: LN1(LReLU(y)) -> 1x1 -> t1
-        {
-            std::vector<ProbSpec> pr;
-            for (int n = 0; n < 2; n++) {
-                const RBParams& rb = c.net[n].rb[r];
-                pr.push_back(ProbSpec{y[n], c.nk, 0, c.nk, in_slab(n, 0), ln ? P + rb.ln1g : none,
-                                      ln ? P + rb.ln1b : none, 1, X + rb.ca.w, X + rb.ca.b, t1[n], c.t1_cs, 0, c.nk,
-                                      none, out_slab(n, 1, 4 * nt1), 0, 1});
-                // training: the full t1_r for the backward's LN2 from the same launch (k_pw's second
-                // store; its dual-store instantiations exist for LN on only -- without LN the separate
-                // launch below writes it)
-                if (ss != nullptr && ln) pr.back().out2 = ST1(n, r);
-            }
-            // only the channels the branches read are stored (into their consumers' sub-tensors when
-            // t1_compact); the LN2 statistics still cover all nk channels
-            const int* t1map = c.t1_compact ? E.p.dtab(c.dev_t1_map) : nullptr;
-            bool dual = false;
-            set_parts(1, conv_launch(E, 1, ROLE_CONV_A, c.hc, c.wc, pr, c.t1_used, nullptr, t1map, nullptr, &dual));
-            dual = dual && ln;   // (out2 is set with LN only: without it k_pw made no second store)
-            if (ss != nullptr && dual) save_stats(1, c.R + 1 + r);
-            if (ss != nullptr && !dual) {
-                // the full t1_r for the backward's LN2 (the compact t1 above holds only the branch windows)
-                std::vector<ProbSpec> pf;
-                for (int n = 0; n < 2; n++) {
-                    const RBParams& rb = c.net[n].rb[r];
-                    pf.push_back(ProbSpec{y[n], c.nk, 0, c.nk, in_slab(n, 0), ln ? P + rb.ln1g : none,
-                                          ln ? P + rb.ln1b : none, 1, X + rb.ca.w, X + rb.ca.b, ST1(n, r), c.nk, 0, c.nk,
-                                          none, Slab{}, 0, 1});
-                }
-                conv_launch(E, 1, ROLE_CONV_A, c.hc, c.wc, pf);
-                save_stats(1, c.R + 1 + r);
-            }
-        }
-        // grouped dilated branches: LN2(LReLU(t1)) -> 3x3 dil d -> t2[:, out_off:out_off+cout]. The k_gc
-        // launch (when planned) takes its branches first; every other branch runs as a k_pw tap-mode
-        // launch over its im2col row when that row fits (9 cin <= 128), the rest as one k_conv<3>.
-        // Each launch's LN3 partial slots follow the previous ones'.
-        int base = 0;
-        std::vector<char> done(nbr, 0);
-        for (const Coupling::GcGroup& gg : c.gcg) {
-            const int ng = (int)gg.br.size();
-            GcArgs ga;
-            std::memset(&ga, 0, sizeof(ga));
-            for (int n = 0; n < 2; n++) {
-                const RBParams& rb = c.net[n].rb[r];
-                ga.in[n] = t1[n];
-                ga.out[n] = t2[n];
-                ga.in_part[n] = ln ? sl[n][1].part : nullptr;
-                ga.out_part[n] = ln ? sl[n][2].part + (size_t)base * LNP : nullptr;   // after earlier launches' slots
-                ga.gamma[n] = ln ? ln2g(rb) : nullptr;
-                ga.beta[n] = ln ? ln2b(rb) : nullptr;
-                for (int k = 0; k < ng; k++) {
-                    ga.w[n][k] = X + rb.gc[gg.br[k]].w;
-                    ga.b[n][k] = X + rb.gc[gg.br[k]].b;
-                }
-            }
-            for (int k = 0; k < ng; k++) {
-                ga.s.br[k] = gg.gcb[k];
-                done[gg.br[k]] = 1;
-            }
-            ga.s.nbr = ng;
-            ga.s.H = c.hc;
-            ga.s.W = c.wc;
-            ga.s.in_cs = c.t1_cs;
-            ga.s.out_cs = c.t2_cs;
-            ga.B = B;
-            ga.s.TH = gg.TH;
-            ga.s.TW = gg.TW;
-            ga.s.tiles_x = gg.tiles_x;
-            ga.s.tiles_per_img = gg.tiles();
-            ga.s.ps = gg.ps;
-            ga.s.nbk = gg.nbk;
-            ga.s.tpp = gg.tpp;
-            ga.s.nw = gg.nw;
-            ga.s.pd = gg.pd;
-            ga.in_nparts = sl[0][1].nparts;
-            ga.part_stride = L.st_parts;
-            // images per workgroup: one workgroup per CU, looping over its images with the next
-            // image's band staged behind the current one's MFMAs
-            // (16 / nw workgroups per CU)
-            const int64_t units = (int64_t)ga.s.tiles_per_img * 2 * B;
-            const int64_t slots = 256LL * gc_wg_per_cu(gg.nw);
-            ga.ipw = (int)std::min<int64_t>(16, std::max<int64_t>(1, (units + slots - 1) / slots));
-#ifdef CNF_DIAG
-            if (const char* e = std::getenv("CNF_GC_IPW")) ga.ipw = std::atoi(e);   // diagnostics
-#endif
-            ga.s.band_bytes = gg.band_bytes;
-            ga.s.lnst = (ga.in_part[0] ? 1 : 0) | (ga.out_part[0] ? 2 : 0);
-            const int gcw = gc_waves(ga);
-            if (base + gcw * ga.s.tiles_per_img > L.st_parts) throw std::runtime_error("k_gc: LN partial slab too small");
-            const int grid_x = ga.s.tiles_per_img * ((B + ga.ipw - 1) / ga.ipw);
-            const int ilds = gg.lds;
-            double fl = 0, by = 0;
-            int win = 0;
-            for (int k = 0; k < ng; k++) {
-                const Branch& b = c.br[gg.br[k]];
-                fl += 2.0 * B * c.hc * c.wc * 9.0 * b.cin * b.cout * 2;
-                win += b.cin;
-                by += 4.0 * B * c.hc * c.wc * b.cout * 2;
-            }
-            by += 4.0 * B * c.hc * c.wc * win * 2 + (ln ? 4.0 * 2 * c.hc * c.wc * win * 2 : 0.0);
-            if (E.p.dry) {
-                bool seen = false;
-                for (const GcShape& o : E.p.gc_launch) seen = seen || std::memcmp(&o, &ga.s, sizeof(GcShape)) == 0;
-                if (!seen) E.p.gc_launch.push_back(ga.s);
-            }
-            E.record("k_gc", fl, by, [ga, grid_x, ilds](void* st) { launch_gc(ga, grid_x, ilds, (hipStream_t)st); });
-            base += gcw * ga.s.tiles_per_img;   // one slot per k_gc wave
-        }
-        {
-            std::vector<ProbSpec> pr;
-            for (int bi = 0; bi < nbr; bi++) {
-                const Branch& b = c.br[bi];
-                if (done[bi] || !(E.p.use_pw && c.net[0].rb[r].gpw[bi].size > 0)) continue;
-                std::vector<ProbSpec> pt;
-                for (int n = 0; n < 2; n++) {
-                    const RBParams& rb = c.net[n].rb[r];
-                    pt.push_back(ProbSpec{t1[n], 9 * b.cin, 0, 9 * b.cin, in_slab(n, 1), ln ? ln2g(rb) : none,
-                                          ln ? ln2b(rb) : none, 1, X + rb.gpw[bi].w, X + rb.gpw[bi].b, t2[n], c.t2_cs,
-                                          b.out_off, b.cout, none, out_slab(n, 2, 0), base, 1});
-                }
-                const int* bmap = c.t2_mapped ? dmap(c.dev_t2_bmap[bi]) : nullptr;
-                TapSrc ts{-1, c.wc, c.t1_pcs[bi], b.cin, c.hc * c.wc * c.t1_cs};
-                ts.dil = b.dil;
-                ts.off = c.t1_off[bi];
-                base += conv_launch(E, 1, ROLE_GC, c.hc, c.wc, pt, ~0ull, &ts, bmap);
-                done[bi] = 1;
-            }
-            int nrest = 0;
-            for (int n = 0; n < 2; n++) {
-                const RBParams& rb = c.net[n].rb[r];
-                int k = 0;
-                for (int bi = 0; bi < nbr; bi++) {
-                    const Branch& b = c.br[bi];
-                    if (done[bi]) continue;
-                    if (c.t1_compact || c.t2_mapped) throw std::logic_error("k_conv<3> branch on a mapped t1 / t2 layout");
-                    pr.push_back(ProbSpec{t1[n], c.nk, b.cin_off, b.cin, in_slab(n, 1), ln ? ln2g(rb) : none,
-                                          ln ? ln2b(rb) : none, 1, X + rb.gc[bi].w, X + rb.gc[bi].b, t2[n], c.gc,
-                                          b.out_off, b.cout, none, out_slab(n, 2, 0), base + k * nt3 * 4, b.dil});
-                    k++;
-                }
-                nrest = k;
-            }
-            if (!pr.empty()) {
-                base += nrest * conv_launch(E, 3, ROLE_GC, c.hc, c.wc, pr);
-            }
-            if (base > L.st_parts) throw std::runtime_error("grouped branches: LN partial slab too small");
-            set_parts(2, base);
-            save_stats(2, 2 * c.R + 1 + r);
-        }
-        // conv_b: LN3(LReLU(t2)) -> 1x1 -> + shortcut -> y (in place)
-        {
-            flush_stats();   // (conv_b writes slab 0's slots: y_r's statistics first)
-            std::vector<ProbSpec> pr;
-            for (int n = 0; n < 2; n++) {
-                const RBParams& rb = c.net[n].rb[r];
-                pr.push_back(ProbSpec{t2[n], c.t2_cs, 0, c.gc, in_slab(n, 2), ln ? ln3g(rb) : none,
-                                      ln ? ln3b(rb) : none, 1, X + rb.cb.w, X + rb.cb.b,
-                                      ss != nullptr ? SY(n, r + 1) : y[n], c.nk, 0, c.nk, y[n],
-                                      out_slab(n, 0, 4 * nt1), 0, 1});
-            }
-            set_parts(0, conv_launch(E, 1, ROLE_CONV_B, c.hc, c.wc, pr, ~0ull, nullptr, nullptr,
-                                     c.t2_mapped ? dmap(c.dev_t2_qmap) : nullptr));
-            if (ss != nullptr)
-                for (int n = 0; n < 2; n++) y[n] = SY(n, r + 1);
-            save_stats(0, r + 1);
-        }
-    }
-    flush_stats();
-    // conv_out: LN_out(LReLU(y)) -> 3x3 -> so (raw A pre-tanh / b); > 64 outputs in 64-channel chunks
-    {
-        std::vector<ProbSpec> pr;
-        for (int n = 0; n < 2; n++) {
-            const NetParams& np = c.net[n];
-            if (!np.co_chunks.empty()) {
-                for (size_t k = 0; k < np.co_chunks.size(); k++)
-                    pr.push_back(ProbSpec{y[n], c.nk, 0, c.nk, in_slab(n, 0), ln ? P + np.ln_out_g : none,
-                                          ln ? P + np.ln_out_b : none, 1, X + np.co_chunks[k].w,
-                                          X + np.co_chunks[k].b, so[n], c.dc2, (int)(64 * k),
-                                          np.co_chunks[k].cout, none, Slab{}, 0, 1});
-                continue;
-            }
-            pr.push_back(ProbSpec{y[n], c.nk, 0, c.nk, in_slab(n, 0), ln ? P + np.ln_out_g : none,
-                                  ln ? P + np.ln_out_b : none, 1, X + np.co.w, X + np.co.b, so[n], c.dc2, 0, c.dc2,
-                                  none, Slab{}, 0, 1});
-        }
-        if (c.net[0].co.fmt == PK_TAP && E.p.tap_pw && 9 * c.dc2 <= c.nk && pr.size() == 2) {
-            // tap GEMM C = LN_out(LReLU(y)) . W_tap as a streamed 1x1 conv into the dead t1 buffer;
-            // k_coupling finishes the 3x3 (tap sums + bias) where it reads s and t
-            for (int n = 0; n < 2; n++) {
-                ProbSpec& q = pr[n];
-                q.bias = X + E.p.aux_zero;
-                q.out = t1[n];
-                q.out_cs = q.cout = 9 * c.dc2;
-                q.out_off = 0;
-                tap_c[n] = t1[n];
-                tap_b[n] = X + c.net[n].co.b;
-            }
-            conv_launch(E, 1, ROLE_CONV_OUT, c.hc, c.wc, pr);
-        } else if (c.net[0].co.fmt == PK_TAP) {
-            convtap_launch(E, c.hc, c.wc, pr);
-        } else {
-            conv_launch(E, 3, ROLE_CONV_OUT, c.hc, c.wc, pr);
-        }
-    }
-    }  // streamed path
-    // affine coupling law + decompress + log-det partials
-    if (defer) {
-        CoupPend& q = *out_pend;
-        q = CoupPend{};
-        q.u = u;
-        q.s_pre = so0;
-        q.t = so1;
-        q.tanh_w = P + c.net[0].tanh_w;
-        q.v = v;
-        q.ld_part = ld_part;
-        q.mask_c = c.mask_c;
-        q.hc = c.hc;
-        q.wc = c.wc;
-        q.dc2 = c.dc2;
-        q.np = E.L.ld_parts;
-        q.on = 1;
-        q.mask = c.mask;
-        q.dc1 = c.dc1;
-        q.W = c.W;
-        q.D = c.D;
-        q.dir = dir;
-        return;
-    }
-    {
-        CoupArgs ca;
-        ca.u = u;
-        ca.v = v;
-        ca.s_pre = so0;
-        ca.t = so1;
-        ca.tanh_w = P + c.net[0].tanh_w;
-        ca.ld_part = ld_part;
-        ca.H = c.H;
-        ca.W = c.W;
-        ca.D = c.D;
-        ca.mask = c.mask;
-        ca.mask_c = c.mask_c;
-        ca.hc = c.hc;
-        ca.wc = c.wc;
-        ca.dc1 = c.dc1;
-        ca.dc2 = c.dc2;
-        ca.dir = dir;
-        for (int n = 0; n < 2; n++) {
-            ca.tc[n] = tap_c[n];
-            ca.tbias[n] = tap_b[n];
-            ca.so_w[n] = n == 0 ? so0 : so1;
-        }
-        const int np = E.L.ld_parts;
-        E.record("k_coupling", 0, 4.0 * B * c.H * c.W * c.D * 2 + 8.0 * B * c.hc * c.wc * c.dc2,
-                 [ca, B, np](void* st) { launch_coupling(ca, B, np, (hipStream_t)st); });
-    }
 }
 
 static void ensure_tables(Plan& p) {
@@ -1303,6 +345,35 @@ size_t cnf_plan_workspace_bytes(const cnf_plan* plan, int B) {
 
 }  // extern "C"
 
+// the layer after li in schedule order (step +1: forward, -1: inverse) that launches anything: squeezes
+// are folded into the factor maps
+struct NextLaunch {
+    const Coupling* coupling = nullptr;   // a coupling layer
+    bool maps = false, end = false;       // a factor boundary (k_map2); nothing: the schedule's tail follows
+};
+static NextLaunch next_launch(const Plan& p, int li, int step) {
+    const int n = (int)p.layers.size();
+    int nx = li + step;
+    while (nx >= 0 && nx < n && p.layers[nx].kind == CNF_LAYER_SQUEEZE) nx += step;
+    NextLaunch r;
+    if (nx < 0 || nx >= n)
+        r.end = true;
+    else if (p.layers[nx].kind == CNF_LAYER_COUPLING)
+        r.coupling = &p.couplings[p.layers[nx].ci];
+    else
+        r.maps = p.layers[nx].kind == CNF_LAYER_FACTOR;
+    return r;
+}
+
+// A k_net_lds layer leaves its coupling law (CoupPend) to the next launch when that is another
+// k_net_lds or the boundary maps; the forward's tail (its final k_map2) applies one too, the inverse
+// ends in the layer that writes xy. Debug option FUSE_COUPLING=0: a k_coupling per layer.
+static bool defers(const Plan& p, const Coupling& c, int li, int step) {
+    if (p.opts.fuse_coupling == 0 || !c.use_lds) return false;
+    const NextLaunch nx = next_launch(p, li, step);
+    return (nx.coupling != nullptr && nx.coupling->use_lds) || nx.maps || (nx.end && step > 0);
+}
+
 // the forward schedule; save_inputs: also copy every coupling layer's input into the training
 // workspace (cnf_flow_forward_train)
 // nz (cnf_flow_forward_noise): xy is the caller's buffer for the noisy input, which the first coupling's
@@ -1333,28 +404,20 @@ static void flow_forward(Plan& p, const float* params, const float* aux, const f
     }
     // a k_net_lds layer followed directly by another one leaves its coupling law to that layer's
     // kernel (CoupPend): no k_coupling launch for it. Not when saving layer inputs (training).
-    const bool fuse = p.opts.fuse_coupling != 0;   // (debug option FUSE_COUPLING=0: a k_coupling per layer)
     CoupPend pend;
     bool have_pend = false;
     // training: a layer whose output is the next coupling's input writes it straight into that coupling's
     // save slot (no copy of every layer input; only the first coupling's, which reads xy)
     auto save_slot_after = [&](size_t li) -> float* {
-        size_t nx = li + 1;
-        while (nx < p.layers.size() && p.layers[nx].kind == CNF_LAYER_SQUEEZE) nx++;
-        if (!save_inputs || nx >= p.layers.size() || p.layers[nx].kind != CNF_LAYER_COUPLING) return nullptr;
-        return E.at<float>(TL.save_u[p.couplings[p.layers[nx].ci].index]);
+        const NextLaunch nx = next_launch(p, (int)li, +1);
+        if (!save_inputs || nx.coupling == nullptr) return nullptr;
+        return E.at<float>(TL.save_u[nx.coupling->index]);
     };
     for (size_t li = 0; li < p.layers.size(); li++) {
         const Layer& ly = p.layers[li];
         if (ly.kind == CNF_LAYER_COUPLING) {
             const Coupling& c = p.couplings[ly.ci];
-            // the next layer that launches anything (squeezes are folded into the factor maps)
-            size_t nx = li + 1;
-            while (nx < p.layers.size() && p.layers[nx].kind == CNF_LAYER_SQUEEZE) nx++;
-            const bool next_lds = nx < p.layers.size() && p.layers[nx].kind == CNF_LAYER_COUPLING &&
-                                  p.couplings[p.layers[nx].ci].use_lds;
-            const bool next_maps = nx >= p.layers.size() || p.layers[nx].kind == CNF_LAYER_FACTOR;
-            const bool defer = fuse && !save_inputs && c.use_lds && (next_lds || next_maps);
+            const bool defer = !save_inputs && defers(p, c, (int)li, +1);
             float* nxt = buf[which];
             if (float* slot = save_slot_after(li)) nxt = slot;
             if (save_inputs && cur != E.at<float>(TL.save_u[c.index])) {
@@ -1366,21 +429,25 @@ static void flow_forward(Plan& p, const float* params, const float* aux, const f
                 });
             }
             CoupPend next;
-            float* save = nullptr;
+            CouplingOpts o;
+            o.pend = have_pend ? &pend : nullptr;
+            o.defer = defer;
+            o.out_pend = &next;
+            o.nz = nz_fused && li == 0 ? nz : nullptr;
             float* so_save[2] = {nullptr, nullptr};
             if (save_inputs && c.lds_bwd) {   // the fused LDS backward's activations
-                save = E.at<float>(TL.act_save[c.index]);
+                o.save = E.at<float>(TL.act_save[c.index]);
                 so_save[0] = E.at<float>(TL.so_save[c.index]);
-                so_save[1] = so_save[0] + (size_t)B * c.hc * c.wc * c.dc2;
             }
-            const TrainLayout::StreamSave* ss =
-                save_inputs && !c.use_lds && TL.has_ssave[c.index] ? &TL.ssave[c.index] : nullptr;
-            if (ss != nullptr) {   // the raw conv_out (k_coupling's so_w in tap mode) into the save area
-                so_save[0] = E.at<float>(ss->so);
-                so_save[1] = so_save[0] + (size_t)B * c.hc * c.wc * c.dc2;
+            if (save_inputs && !c.use_lds && TL.has_ssave[c.index]) {
+                o.ss = &TL.ssave[c.index];
+                so_save[0] = E.at<float>(o.ss->so);   // the raw conv_out (k_coupling's so_w in tap mode) into the save area
             }
-            run_coupling(E, c, cur, nxt, ld + (size_t)c.index * B * L.ld_parts, +1, have_pend ? &pend : nullptr,
-                         defer, &next, save, (save || ss) ? so_save : nullptr, ss, nz_fused && li == 0 ? nz : nullptr);
+            if (o.save != nullptr || o.ss != nullptr) {
+                so_save[1] = so_save[0] + (size_t)B * c.hc * c.wc * c.dc2;
+                o.so_save = so_save;
+            }
+            run_coupling(E, c, cur, nxt, ld + (size_t)c.index * B * L.ld_parts, +1, o);
             pend = next;
             have_pend = defer;
             cur = nxt;
@@ -1594,7 +661,6 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
     // deferred inverse law (as the forward's, CoupPend::dir = -1): an LDS layer whose successor in
     // the inverse order (the previous layer by index) launches k_net_lds or the boundary maps leaves
     // its law to that kernel — no k_coupling launch for it
-    const bool fuse = p.opts.fuse_coupling != 0;   // (debug option FUSE_COUPLING=0: a k_coupling per layer)
     CoupPend pend;
     bool have_pend = false;
     int bi = (int)p.boundaries.size() - 1;
@@ -1602,17 +668,15 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
         const Layer& ly = p.layers[li];
         if (ly.kind == CNF_LAYER_COUPLING) {
             const Coupling& c = p.couplings[ly.ci];
-            int nx = li - 1;
-            while (nx >= 0 && p.layers[nx].kind == CNF_LAYER_SQUEEZE) nx--;
-            const bool next_lds = nx >= 0 && p.layers[nx].kind == CNF_LAYER_COUPLING &&
-                                  p.couplings[p.layers[nx].ci].use_lds;
-            const bool next_maps = nx >= 0 && p.layers[nx].kind == CNF_LAYER_FACTOR;
-            const bool defer = fuse && c.use_lds && (next_lds || next_maps);
             float* nxt = li == first ? xy : buf[which];
             CoupPend next;
-            run_coupling(E, c, cur, nxt, nullptr, -1, have_pend ? &pend : nullptr, defer, &next);
+            CouplingOpts o;
+            o.pend = have_pend ? &pend : nullptr;
+            o.defer = defers(p, c, li, -1);
+            o.out_pend = &next;
+            run_coupling(E, c, cur, nxt, nullptr, -1, o);
             pend = next;
-            have_pend = defer;
+            have_pend = o.defer;
             cur = nxt;
             which ^= 1;
         } else if (ly.kind == CNF_LAYER_FACTOR) {
@@ -1919,19 +983,9 @@ int cnf_debug_pw_shapes(cnf_plan* plan, int B, int* words, int cap) {
     if (!plan || !words || B <= 0) return -1;
     Plan& p = *plan->p;
     CNF_TRY
-    p.dry = true;
     p.pw_shapes.clear();
     p.gc_launch.clear();
-    char* fake = reinterpret_cast<char*>(uintptr_t(1) << 40);   // never dereferenced
-    try {
-        flow_forward(p, (const float*)fake, (const float*)fake, (const float*)fake, (float*)fake, (float*)fake, fake, B,
-                     nullptr, false);
-    } catch (...) {
-        p.dry = false;
-        throw;
-    }
-    p.dry = false;
-    p.recorded.clear();
+    dry_run(p, B, +1);
     const int n = (int)p.pw_shapes.size() * PWSHAPE_WORDS;
     if (n > cap) return -1;
     for (size_t i = 0; i < p.pw_shapes.size(); i++)
@@ -1954,25 +1008,8 @@ int cnf_debug_gc_shape(const cnf_plan* plan, int coupling, int* words, int cap) 
     if (cap < GCSHAPE_WORDS * (int)c.gcg.size()) return -1;
     int n = 0;
     for (const Coupling::GcGroup& gg : c.gcg) {
-        GcShape s;
-        std::memset(&s, 0, sizeof(s));
-        for (size_t k = 0; k < gg.br.size(); k++) s.br[k] = gg.gcb[k];
-        s.nbr = (int)gg.br.size();
-        s.H = c.hc;
-        s.W = c.wc;
-        s.in_cs = c.t1_cs;   // as run_coupling launches it
-        s.out_cs = c.t2_cs;
-        s.TH = gg.TH;
-        s.TW = gg.TW;
-        s.tiles_x = gg.tiles_x;
-        s.tiles_per_img = gg.tiles();
-        s.ps = gg.ps;
-        s.nbk = gg.nbk;
-        s.tpp = gg.tpp;
-        s.nw = gg.nw;
-        s.pd = gg.pd;
-        s.band_bytes = gg.band_bytes;
-        s.lnst = p.desc.layer_norm ? 3 : 0;   // the forward's k_gc: LN2 on load and LN3 partials iff LayerNorm
+        // the forward's k_gc: LN2 on load and LN3 partials iff LayerNorm
+        const GcShape s = gc_shape(c, gg, p.desc.layer_norm ? 3 : 0);
         std::memcpy(words + n, &s, sizeof(s));
         n += GCSHAPE_WORDS;
     }
