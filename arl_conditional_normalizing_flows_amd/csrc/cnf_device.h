@@ -228,12 +228,22 @@ __device__ __forceinline__ void ln_fold(const f4 v, float& n, float& m, float& M
 __device__ __forceinline__ void ln_wave_final(float n, float m, float M2, float& mu, float& rstd) {
     const float N = wave_sum_f(n);
     const float iN = __builtin_amdgcn_rcpf(N);
-    const float mean = wave_sum_f(n * m) * iN;
+    // the lanes' means are merged as offsets from lane 0's (it folds slot 0; a lane without partials has
+    // n = 0 and adds nothing): sum n m * rcp(N) rounds, and the approximate reciprocal errs, relative to
+    // the mean, which costs the normalised values their low bits when the mean is far above the spread
+    // and makes a constant image's mean inexact
+    const float m0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
+    const float mean = fmaf(wave_sum_f(n * (m - m0)), iN, m0);
     const float d = m - mean;
     const float M = wave_sum_f(fmaf(n * d, d, M2));
     mu = mean;
     rstd = __builtin_amdgcn_rsqf(fmaf(M, iN, LN_EPS));
 }
+// Consumers normalise as (t - mean) * rstd, then one fma with gamma / beta. The shorter fma(t, rstd, nmr)
+// with nmr = -mean * rstd rounded once has an absolute error of 2^-24 |mean| / sigma on the normalised
+// value: harmless while |mean| / sigma is of order 1, and the whole result once the mean is far above the
+// spread (a constant image normalised to rounding noise instead of 0; tests/test_value_regimes.py,
+// lnconst / lnoffset). The subtraction costs one VALU operation per element.
 // a lane's first partial: its (n, mean, M2) directly (no merge with the empty state, whose
 // n * rcp(n) need not be exactly 1)
 __device__ __forceinline__ void ln_fold_first(const f4 v, float& n, float& m, float& M2) {

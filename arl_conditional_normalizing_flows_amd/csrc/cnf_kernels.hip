@@ -546,7 +546,9 @@ __global__ __launch_bounds__(256) void k_ln_merge(float* __restrict__ part0, flo
     }
     // wave: N = sum n, mean = sum n m / N, M2 = sum (M2 + n (m - mean)^2)
     const float N = wave_sum_f(n);
-    const float mean = N > 0.f ? wave_sum_f(n * m) / N : 0.f;
+    // (offsets from lane 0's mean, as ln_wave_final; a wave without slots has m = m0 = 0)
+    const float m0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
+    const float mean = N > 0.f ? m0 + wave_sum_f(n * (m - m0)) / N : 0.f;
     const float d = m - mean;
     const float M = wave_sum_f(fmaf(n * d, d, M2));
     __shared__ float wv[4][3];

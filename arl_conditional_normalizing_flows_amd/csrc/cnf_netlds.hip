@@ -107,6 +107,9 @@ __device__ __forceinline__ void lst_final(const float* slots, float& mu, float& 
     for (int w = 0; w < NW; w++) q[w] = *reinterpret_cast<const f4*>(slots + 4 * w);
     float n[NW], m[NW], M2[NW];
     float N = 0.f, S = 0.f;
+    // the wave means are merged as offsets from wave 0's (sum n_w m_w / N rounds, and its approximate
+    // reciprocal errs, relative to the mean: a mean far above the spread, or a constant image, then
+    // loses the normalised values' low bits). A wave without values has n_w = 0 and adds nothing.
 #pragma unroll
     for (int w = 0; w < NW; w++) {
         n[w] = q[w][3];
@@ -114,10 +117,10 @@ __device__ __forceinline__ void lst_final(const float* slots, float& mu, float& 
         m[w] = q[w][0] + r;
         M2[w] = fmaxf(fmaf(-q[w][1], r, q[w][2]), 0.f);
         N += n[w];
-        S = fmaf(n[w], m[w], S);
+        S = fmaf(n[w], m[w] - m[0], S);
     }
     const float iN = __builtin_amdgcn_rcpf(N);
-    const float mean = S * iN;
+    const float mean = fmaf(S, iN, m[0]);
     float M = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; w++) {
@@ -135,7 +138,6 @@ __device__ __forceinline__ void ln_apply(const float* src, int sstride, float* d
                                          int nc, int C_ln, float mu, float rstd, const float* __restrict__ g,
                                          const float* __restrict__ b, bool ln) {
     const int n = HW * nc;
-    const float nmr = -mu * rstd;
     if (((sstride | dstride | nc | c0 | C_ln) & 3) == 0) {
         const int n4 = n >> 2, C4 = nc >> 2;
         const bool full = (c0 == 0 && nc == C_ln);   // gamma/beta contiguous over the whole image
@@ -163,7 +165,7 @@ __device__ __forceinline__ void ln_apply(const float* src, int sstride, float* d
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float t = lrelu_(x[j]);
-                    x[j] = ln ? fmaf(fmaf(t, rstd, nmr), gv[u][j], bv[u][j]) : t;
+                    x[j] = ln ? fmaf((t - mu) * rstd, gv[u][j], bv[u][j]) : t;
                 }
                 *reinterpret_cast<f4*>(dst + p * dstride + c) = x;
             }
@@ -193,7 +195,7 @@ __device__ __forceinline__ void ln_apply(const float* src, int sstride, float* d
             const int e = base + u * NT + threadIdx.x;
             if (e >= n) continue;
             const float t = lrelu_(xv[u]);
-            dst[pp[u] * dstride + c0 + cc[u]] = ln ? fmaf(fmaf(t, rstd, nmr), gv[u], bv[u]) : t;
+            dst[pp[u] * dstride + c0 + cc[u]] = ln ? fmaf((t - mu) * rstd, gv[u], bv[u]) : t;
         }
     }
 }
@@ -237,7 +239,6 @@ __device__ __forceinline__ void ln_full(const float* src, int sstride, float* ds
                                         float mu, float rstd, const LnPre& L, const float* __restrict__ g,
                                         const float* __restrict__ b) {
     const int C4 = C >> 2, n4 = HW * C4;
-    const float nmr = -mu * rstd;
 #pragma unroll
     for (int u = 0; u < GPF; u++) {
         const int i = u * NT + (int)threadIdx.x;
@@ -245,7 +246,7 @@ __device__ __forceinline__ void ln_full(const float* src, int sstride, float* ds
             const int p = i / C4, c = (i - p * C4) << 2;
             f4 x = *reinterpret_cast<const f4*>(src + p * sstride + c);
 #pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = fmaf(fmaf(lrelu_(x[j]), rstd, nmr), L.g[u][j], L.b[u][j]);
+            for (int j = 0; j < 4; j++) x[j] = fmaf((lrelu_(x[j]) - mu) * rstd, L.g[u][j], L.b[u][j]);
             *reinterpret_cast<f4*>(dst + p * dstride + c) = x;
         }
     }
@@ -268,7 +269,7 @@ __device__ __forceinline__ void ln_full(const float* src, int sstride, float* ds
             const int p = i / C4, c = (i - p * C4) << 2;
             f4 x = xv[u];
 #pragma unroll
-            for (int j = 0; j < 4; j++) x[j] = fmaf(fmaf(lrelu_(x[j]), rstd, nmr), gv[u][j], bv[u][j]);
+            for (int j = 0; j < 4; j++) x[j] = fmaf((lrelu_(x[j]) - mu) * rstd, gv[u][j], bv[u][j]);
             *reinterpret_cast<f4*>(dst + p * dstride + c) = x;
         }
     }
@@ -282,7 +283,6 @@ __device__ __forceinline__ void ln_windows(float* buf, int stride, int HW, int C
                                            const float* __restrict__ b, bool ln) {
     int total = 0;
     for (int k = 0; k < nwin; k++) total += HW * wlen[k];
-    const float nmr = -mu * rstd;
     constexpr int US = 8;
     for (int base = 0; base < total; base += NT * US) {
         int pos[US], gi[US];
@@ -314,7 +314,7 @@ __device__ __forceinline__ void ln_windows(float* buf, int stride, int HW, int C
         for (int u = 0; u < US; u++) {
             if (pos[u] < 0) continue;
             const float t = lrelu_(xv[u]);
-            buf[pos[u]] = ln ? fmaf(fmaf(t, rstd, nmr), gv[u], bv[u]) : t;
+            buf[pos[u]] = ln ? fmaf((t - mu) * rstd, gv[u], bv[u]) : t;
         }
     }
 }
@@ -367,6 +367,16 @@ struct Epi {
             const float b = bias != nullptr ? bias[chv[n] ? ch : 0] : 0.f;   // unconditional LDS read
             bz[n] = chv[n] ? b : 0.f;
         }
+    }
+    // the value store() writes for lane 0's first element of subtile sb (pixel 16 sb, channel oc0), by
+    // store()'s own expression: the LN statistics' shift. With a residual the stored value is shortcut +
+    // branch, and a shift taken from the branch alone leaves sum (x - K)^2 to cancel whenever the
+    // residual stream's mean is far above its spread.
+    __device__ __forceinline__ float sample(const f4 (&acc)[NR], int sb, const float* out, int ostride,
+                                            bool residual) const {
+        float v = acc[0][0] + bz[0];
+        if (residual) v += out[sb * 16 * ostride];
+        return v;
     }
     // write subtile sb of acc; out points at channel oc0 of pixel 0
     __device__ __forceinline__ void store(const f4 (&acc)[NR], int sb, int HW, float* out, int ostride, bool residual,
@@ -436,7 +446,7 @@ __device__ __forceinline__ void ks_finish(f4 (&acc)[NR], int s, int k, int KS, i
 #pragma unroll
             for (int n = 0; n < NR; n++)
                 acc[n] += *reinterpret_cast<const f4*>(b + ((((kk - 1) * nsub + s) * NR + n) * 64 + lane) * 4);
-        if (stats) lst_setk(st, acc[0][0] + ep.bz[0]);
+        if (stats) lst_setk(st, ep.sample(acc, s, out, ostride, residual));
         ep.store(acc, s, HW, out, ostride, residual, stats, st);
     }
 }
@@ -518,7 +528,7 @@ __device__ __forceinline__ void conv1_lds(const float* in, int istride, int cin,
                     acc1[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s], bq[n][s], acc1[n], 0, 0, 0);
                 }
         }
-        if (stats) lst_setk(st, acc0[0][0] + ep.bz[0]);
+        if (stats) lst_setk(st, ep.sample(acc0, s0, out, ostride, residual));
         ep.store(acc0, s0, HW, out, ostride, residual, stats, st);
         if (v1) ep.store(acc1, s1, HW, out, ostride, residual, stats, st);
     }

@@ -276,14 +276,14 @@ __global__ __launch_bounds__(64 * PW_NW, CNF_PW_MINW) void k_pw(ConvArgs a) {
     auto step = [&](int ii, f4 (&xc)[GX], float (&rc)[NR][4], int pf) {
         const int img = img0 + ii;
         const float rs = LN ? lstat[2 * ii + 1] : 1.f;
-        const float nmr = LN ? -lstat[2 * ii] * rs : 0.f;
+        const float mu = LN ? lstat[2 * ii] : 0.f;   // (t - mu) * rs, not fma(t, rs, -mu * rs): cnf_device.h
         f4 av[GX];
 #pragma unroll
         for (int g = 0; g < GX; g++) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const float v = !TAP || P.act ? lrelu(xc[g][j]) : xc[g][j];   // conv_in reads raw u
-                av[g][j] = LN ? fmaf(fmaf(v, rs, nmr), gm[g][j], bt[g][j]) : v;
+                av[g][j] = LN ? fmaf((v - mu) * rs, gm[g][j], bt[g][j]) : v;
             }
         }
         float res[NR][4];
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(GC_NTS, SID >= 0 ? 16 / GC_NWS : 1) void k_gc(GcArg
     // outside the image / window
     auto store_img = [&](int ii, const f4 (&xs)[GC_GQ]) {
         const float rs = ln ? lstat[2 * ii + 1] : 1.f;
-        const float nmr = ln ? -lstat[2 * ii] * rs : 0.f;
+        const float mu = ln ? lstat[2 * ii] : 0.f;   // (as k_pw)
         unsigned char* dst = smem + (ii & 1) * GS(band_bytes);
 #pragma unroll
         for (int u = 0; u < GC_GQ; u++) {
@@ -806,7 +806,7 @@ __global__ __launch_bounds__(GC_NTS, SID >= 0 ? 16 / GC_NWS : 1) void k_gc(GcArg
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float t = lrelu(xs[u][j]);
-                    v[j] = ln ? fmaf(fmaf(t, rs, nmr), gq[u][j], bq[u][j]) : t;
+                    v[j] = ln ? fmaf((t - mu) * rs, gq[u][j], bq[u][j]) : t;
                 }
             }
             bf16x4 h, m, l;

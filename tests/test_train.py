@@ -191,13 +191,14 @@ def test_gradients_match_oracle(gpu, name, B, extra):
     check_gradients(gpu, kw, xy, options, f'{name} {extra}', perturb)
 
 
-def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None):
-    """The HIP gradient of the flow cFlow(**kw) at xy (weights init_params(5)) and its 4 loss terms against
-    float64 autograd, under the module docstring's bar. perturb: None (no perturbation term) or (eps list,
-    seeds per eps). refs: (G_ref, terms_ref, G32) of this kw and xy when the caller has them already."""
+def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None, params=None):
+    """The HIP gradient of the flow cFlow(**kw) at xy (weights params, by default init_params(5)) and its 4
+    loss terms against float64 autograd, under the module docstring's bar. perturb: None (no perturbation
+    term) or (eps list, seeds per eps). refs: (G_ref, terms_ref, G32) of this kw, xy and params when the
+    caller has them already."""
     B = xy.shape[0]
     ora = OracleCFlow(**kw)
-    P = ora.init_params(5)
+    P = ora.init_params(5) if params is None else params
     if refs is None:
         G_ref, terms_ref = oracle_grads(kw, P, xy)
         G32, _ = oracle_grads(kw, P, xy, torch.float32)
@@ -280,8 +281,22 @@ def test_train_step_adam_update_and_descent(gpu):
     out = flow.train_step(xy)
     assert set(out) == {'loss', 'z_loss', 'y_loss', 'detJ_loss'}
     p1 = flow.params.detach().cpu().numpy().astype(np.float64)
-    exp, _, _ = adam_np(p0, g, np.zeros_like(g), np.zeros_like(g), 1, lr=1e-5)
+    lr = 1e-5
+    exp, _, _ = adam_np(p0, g, np.zeros_like(g), np.zeros_like(g), 1, lr=lr)
     assert np.max(np.abs(p1 - exp)) <= 1e-6 + 1e-5 * np.max(np.abs(exp))
+    # the bound above is wider than the update itself (|update| <= lr, the bound ~ 1e-5 max|p|). The update:
+    # on the elements whose gradient is not near 0 within its tensor, to 1e-3 lr plus the fp32 rounding of
+    # the parameter (the rule of test_training_driver.test_fit_trajectory_matches_float64_oracle)
+    n_checked = 0
+    for n, o, s in flow.param_specs:
+        sl = slice(o, o + (int(np.prod(s)) if s else 1))
+        ga = np.abs(g[sl])
+        big = ga > 1e-3 * max(float(ga.max()), 1e-30)
+        d = np.abs((p1[sl] - p0[sl]) - (exp[sl] - p0[sl]))
+        tol = 1e-3 * lr + 2.0 ** -23 * np.abs(exp[sl])
+        assert np.all(d[big] <= tol[big]), (n, float(np.max(d[big] / tol[big])))
+        n_checked += int(big.sum())
+    assert n_checked >= 0.5 * g.size, (n_checked, g.size)
     # a few more steps on the same batch lower the loss
     losses = [out['loss']]
     for _ in range(5):
@@ -293,6 +308,62 @@ def test_train_step_adam_update_and_descent(gpu):
     zy, _ = flow(xy, 1)
     x2 = flow(zy, -1)
     assert float((x2 - xy).abs().max()) <= 1e-4 * float(xy.abs().max())
+
+
+@pytest.mark.gpu
+def test_adam_step_matches_float64(gpu):
+    """cnf_adam_step (k_adam) alone against adam_np in float64: n = 8192 * 256 + 37, so the grid-stride
+    loop (the launch is capped at 8192 workgroups of 256) and a ragged tail both run; non-zero m and v
+    (and a zero block); steps 1, 2 and 1000; gradients over seven decades with 0, +-1e-20 (g^2 underflows:
+    epsilon decides) and +-1e3 placed at the start and in the tail. p, m and v to the fp32 rounding of the
+    float64 result, each bound the sum of the roundings of the kernel's own operations (eps = 2^-24):
+      m' = m + (g - m) c1            : eps (2 c1 |g - m| + |m'|)
+      v' = v + (g g - v) c2          : eps (c2 (g^2 + 2 |g^2 - v|) + |v'|), plus the smallest normal (g^2 may flush)
+      p' = p - alpha m' / (sqrt(v') + epsilon): the above carried through (|sqrt a - sqrt b| <= min(|a - b| /
+           (2 sqrt b), sqrt|a - b|)), 6 eps of the quotient for sqrt, the sum, alpha, the product and the
+           division, and eps |p'|.
+    The reference takes lr, beta and epsilon as the fp32 values the C ABI passes."""
+    from arl_conditional_normalizing_flows_amd import _lib
+    from arl_conditional_normalizing_flows_amd._lib import check, ptr
+    lib = _lib.load()
+    n = 8192 * 256 + 37
+    rng = np.random.default_rng(21)
+    p0 = rng.standard_normal(n).astype(np.float32)
+    g = (rng.standard_normal(n) * 10.0 ** rng.uniform(-6, 1, n)).astype(np.float32)
+    m0 = rng.normal(0, 0.1, n).astype(np.float32)
+    v0 = (rng.standard_normal(n) ** 2 * 1e-2).astype(np.float32)
+    special = np.array([0.0, 1e-20, -1e-20, 1e3, -1e3], np.float32)
+    for at in (0, 8192 * 256 + 20):              # first workgroup, and the ragged tail
+        g[at:at + 5] = special
+    for at in (5, 8192 * 256 + 25):              # the same gradients on zero moments
+        g[at:at + 5] = special
+        m0[at:at + 5] = 0
+        v0[at:at + 5] = 0
+    m0[1000:2000] = 0
+    v0[1000:2000] = 0
+    lr, b1, b2, epsilon = (float(np.float32(x)) for x in (1e-3, 0.9, 0.999, 1e-7))
+    eps = 2.0 ** -24
+    for step in (1, 2, 1000):
+        p, m, v = (torch.from_numpy(a.copy()).to(gpu) for a in (p0, m0, v0))
+        check(lib.cnf_adam_step(ptr(p), ptr(torch.from_numpy(g).to(gpu)), ptr(m), ptr(v), n, lr, b1, b2, epsilon, step,
+                                torch.cuda.current_stream().cuda_stream), 'cnf_adam_step')
+        torch.cuda.synchronize()
+        P0, G, M0, V0 = (a.astype(np.float64) for a in (p0, g, m0, v0))
+        pr, mr, vr = adam_np(P0, G, M0, V0, step, lr=lr, b1=b1, b2=b2, eps=epsilon)
+        c1, c2 = 1 - b1, 1 - b2
+        alpha = lr * math.sqrt(1 - b2 ** step) / (1 - b1 ** step)
+        tol_m = eps * (2 * c1 * np.abs(G - M0) + np.abs(mr))
+        tol_v = eps * (c2 * (G * G + 2 * np.abs(G * G - V0)) + np.abs(vr)) + 2.0 ** -126
+        rv = np.sqrt(vr)
+        d_sqrt = np.minimum(tol_v / (2 * np.maximum(rv, 1e-300)), np.sqrt(tol_v))
+        den = rv + epsilon
+        q = alpha * np.abs(mr) / den
+        tol_p = alpha * tol_m / den + q * d_sqrt / den + 6 * eps * q + eps * np.abs(pr)
+        for what, got, ref, tol in (('m', m, mr, tol_m), ('v', v, vr, tol_v), ('p', p, pr, tol_p)):
+            e = np.abs(got.cpu().numpy().astype(np.float64) - ref)
+            print(f'adam step {step} {what}: worst error / bound {np.max(e / np.maximum(tol, 1e-300)):.3f}')
+            assert np.all(e <= tol), (step, what, int(np.argmax(e / tol)), float(np.max(e / np.maximum(tol, 1e-300))))
+        assert not np.array_equal(p.cpu().numpy()[-37:], p0[-37:])   # the tail was updated
 
 
 @pytest.mark.gpu
