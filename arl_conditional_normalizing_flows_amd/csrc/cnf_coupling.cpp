@@ -653,11 +653,10 @@ struct TrainSave {
     const TrainLayout::StreamSave* ss;
     bool ln;
     LnFinalSet pend{};
+    const LnIndex idx{c.R};
+    const StreamActs acts = ss != nullptr ? StreamActs::saved(E.ws, *ss, E.B, c) : StreamActs{};
 
     bool on() const { return ss != nullptr; }
-    float* y(int n, int r) const { return E.at<float>(ss->y[n]) + (size_t)r * E.B * c.hc * c.wc * c.nk; }
-    float* t1(int n, int r) const { return E.at<float>(ss->t1[n]) + (size_t)r * E.B * c.hc * c.wc * c.nk; }
-    float* t2(int n, int r) const { return E.at<float>(ss->t2[n]) + (size_t)r * E.B * c.hc * c.wc * c.gc; }
 
     void flush() {
         if (pend.count == 0) return;
@@ -668,14 +667,14 @@ struct TrainSave {
         E.record("k_ln_final", 0, bytes, [=](void* st) { launch_ln_final(fs, B, (hipStream_t)st); });
         pend.count = 0;
     }
-    // the statistics of LN tensor i (see TrainLayout::StreamSave) from the slots of its slab
+    // the statistics of LN tensor i (an LnIndex number) from the slots of its slab
     void stats(const Slab (&sl)[2], int i) {
         if (!on() || !ln) return;
         if (pend.count == LNF_MAX) flush();
         const int q = pend.count++;
         for (int n = 0; n < 2; n++) {
             pend.part[q][n] = sl[n].part;
-            pend.st[q][n] = E.at<float>(ss->st[n]) + (size_t)i * E.B * 2;
+            pend.st[q][n] = acts.stats(n, i);
         }
         pend.nparts[q] = sl[0].nparts;
     }
@@ -701,9 +700,9 @@ struct Streamed {
         const WsLayout& L = E.L;
         if (ss != nullptr && c.t2_mapped) throw std::logic_error("training save: mapped t2 layout");
         for (int n = 0; n < 2; n++) {
-            y[n] = sv.on() ? sv.y(n, 0) : E.at<float>(L.y[n]);
+            y[n] = sv.on() ? sv.acts.y(n, 0) : E.at<float>(L.y[n]);
             t1[n] = E.at<float>(L.t1[n]);
-            t2[n] = sv.on() ? sv.t2(n, 0) : E.at<float>(L.t2[n]);
+            t2[n] = sv.on() ? sv.acts.t2(n, 0) : E.at<float>(L.t2[n]);
             for (int k = 0; k < 3; k++) sl[k][n].part = E.at<float>(L.st_part[n][k]);
         }
         sv.pend.part_stride = L.st_parts;
@@ -757,7 +756,7 @@ struct Streamed {
             });
             set_parts(SL_Y, conv3_launch(E, ROLE_CONV_IN, c.hc, c.wc, pr));
         }
-        sv.stats(sl[SL_Y], 0);
+        sv.stats(sl[SL_Y], sv.idx.ln1(0));
     }
 
     // conv_a: LN1(LReLU(y)) -> 1x1 -> t1. Only the channels the branches read are stored (into their
@@ -773,7 +772,7 @@ struct Streamed {
             pr.back().store_mask = c.t1_used;
             // training: the full t1_r for the backward's LN2 from the same launch (k_pw's second
             // store; its dual-store instantiations exist for LN on only)
-            if (sv.on() && ln) x.out2[n] = sv.t1(n, r);
+            if (sv.on() && ln) x.out2[n] = sv.acts.t1(n, r);
         }
         const Launched1x1 l = conv1x1_launch(E, ROLE_CONV_A, c.hc, c.wc, pr, x);
         set_parts(SL_T1, l.slots);
@@ -781,13 +780,13 @@ struct Streamed {
         if (!(l.pw && ln)) {
             // no second store: the full t1_r by a launch of its own (the t1 above holds only the branch windows)
             for (int n = 0; n < 2; n++) {
-                pr[n].out = dst(sv.t1(n, r), c.nk);
+                pr[n].out = dst(sv.acts.t1(n, r), c.nk);
                 pr[n].out_st = Slab{};
                 pr[n].store_mask = ~0ull;
             }
             conv1x1_launch(E, ROLE_CONV_A, c.hc, c.wc, pr);
         }
-        sv.stats(sl[SL_T1], c.R + 1 + r);
+        sv.stats(sl[SL_T1], sv.idx.ln2(r));
     }
 
     // LN2 gamma/beta in t1's layout: the aux copies gathered to the compact layout, or the parameters
@@ -897,7 +896,7 @@ struct Streamed {
         conv3_branches(r, done);
         if (base > E.L.st_parts) throw std::runtime_error("grouped branches: LN partial slab too small");
         set_parts(SL_T2, base);
-        sv.stats(sl[SL_T2], 2 * c.R + 1 + r);
+        sv.stats(sl[SL_T2], sv.idx.ln3(r));
     }
 
     // conv_b: LN3(LReLU(t2)) -> 1x1 -> + shortcut -> y (in place; training: the next save slice)
@@ -909,14 +908,14 @@ struct Streamed {
             const LnLoad l3 = c.t2_mapped ? ln_load(SL_T2, n, X + rb.ln3c_g, X + rb.ln3c_b)
                                           : ln_load(SL_T2, n, P + rb.ln3g, P + rb.ln3b);
             pr.push_back(ProbSpec(Src{t2[n], c.t2_cs, 0, c.gc}, l3, 1, packed(rb.cb),
-                                  dst(sv.on() ? sv.y(n, r + 1) : y[n], c.nk), slab(SL_Y, n)));
+                                  dst(sv.on() ? sv.acts.y(n, r + 1) : y[n], c.nk), slab(SL_Y, n)));
             pr.back().res = y[n];
         }
         PwExtras x;
         x.in_map = c.t2_mapped ? E.p.dtab(c.dev_t2_qmap) : nullptr;
         set_parts(SL_Y, conv1x1_launch(E, ROLE_CONV_B, c.hc, c.wc, pr, x).slots);
         for (int n = 0; n < 2; n++) y[n] = pr[n].out.ptr;
-        sv.stats(sl[SL_Y], r + 1);
+        sv.stats(sl[SL_Y], sv.idx.ln1(r + 1));   // (ln_out() after the last block)
     }
 
     // conv_out: LN_out(LReLU(y)) -> 3x3 -> so (raw A pre-tanh / b); > 64 outputs in 64-channel chunks
@@ -955,7 +954,7 @@ struct Streamed {
         conv_in(u);
         for (int r = 0; r < c.R; r++) {
             if (sv.on())
-                for (int n = 0; n < 2; n++) t2[n] = sv.t2(n, r);
+                for (int n = 0; n < 2; n++) t2[n] = sv.acts.t2(n, r);
             conv_a(r);
             grouped(r);
             conv_b(r);

@@ -37,18 +37,28 @@ struct Options {
     int layout = 7;          // LAYOUT bits: 1 compact t1 sub-tensors, 2 mapped t2 sub-tensors, 4 polyphase k_gc tiles
     int fuse_coupling = 1;   // FUSE_COUPLING: 0 = every coupling layer launches its own k_coupling
     int lds_bwd = 2;         // LDS_BWD: 0 multi-kernel backward of the k_net_lds layers, 1 fused (one launch), 2 fused split
-    // TRAIN_ALT bits, alternative training kernels: 1 VALU convolutions, 2 LDS-staged band weight gradients
-    // (no k_wgrad_direct), 4 no band-staged transposed conv, 8 no thin-channel kernels, 16 a separate
-    // LN-backward reduction kernel, 32 a zeroed dt1 gradient instead of the LN2 channel mask
-    int train_alt = 0;
-    // TRAIN_SCHED bits: 1 weight gradients on the chain streams, 2 recompute the streamed activations
-    // (no saves), 4 enqueue net A's chain before net b's (no interleaving)
-    int train_sched = 0;
+    int train_alt = 0;       // TRAIN_ALT: a sum of the ALT_* bits below
+    int train_sched = 0;     // TRAIN_SCHED: a sum of the SCHED_* bits below
     // SCHEDULE_CHECK: 1 = cnf_plan_create dry-runs the forward / inverse schedule and refuses a flow they
     // cannot run; 0 = the plan tables alone (such a plan fails in its first forward or inverse). Unset (-1):
     // 1 for CNF_GROUP_REFERENCE, 0 for CNF_GROUP_INTENDED, whose plans of flows with streamed layers
     // (dense grouped image over the LDS budget) serve host-side table checks; cFlow always asks for 1
     int schedule_check = -1;
+};
+// TRAIN_ALT bits: alternative training kernels, each the reference of a parity test or a fallback
+enum : int {
+    ALT_VALU = 1,            // every training convolution on the register-blocked VALU kernels (k_tconv, k_wgrad)
+    ALT_WGRAD_BAND = 2,      // LDS-staged band weight gradients (k_wgrad_band) instead of k_wgrad_direct
+    ALT_NO_TCONV_BAND = 4,   // no band-staged 3x3 transposed convolution (k_tconv_band)
+    ALT_NO_THIN = 8,         // no thin-channel kernels (k_tconv_thin, k_wgrad_thin): the MFMA kernels take those convs
+    ALT_LNB_REDUCE = 16,     // the LN backward's reduction as its own kernel (k_lnb_reduce), not in the producing data gradient
+    ALT_ZERO_DT1 = 32,       // dt1's gradient buffer zeroed before the grouped branches instead of the LN2 channel mask
+};
+// TRAIN_SCHED bits: how the streamed layers' backward is scheduled
+enum : int {
+    SCHED_WGRAD_ON_CHAIN = 1,   // weight gradients on the chain streams (no weight-gradient streams)
+    SCHED_RECOMPUTE = 2,        // recompute the streamed layers' activations in the backward (the forward saves none)
+    SCHED_NET_OUTER = 4,        // enqueue net A's whole chain before net b's (no interleaving)
 };
 // parses a debug_options string (null / empty: defaults); throws std::invalid_argument on an unknown
 // name or a malformed value (cnf_runtime.cpp)

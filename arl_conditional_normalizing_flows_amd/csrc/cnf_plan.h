@@ -214,13 +214,69 @@ struct TrainLayout {
     size_t rows2 = 0, gsave[2] = {}, dso_l[2][2] = {};
     int gsave_max = 0;
     // streamed layers: the training forward saves the activations the backward would otherwise recompute
-    // (when they fit the budget): per net y [R+1][B][HW][nk], full t1 [R][B][HW][nk], t2 [R][B][HW][gc],
-    // LN statistics [3R+1][B][2] (y_r: r, t1_r: R+1+r, t2_r: 2R+1+r) and the raw conv_out [2][B][HW][dc2]
+    // (when they fit the budget); the regions' contents and sizes: StreamActs below
     struct StreamSave {
         size_t y[2] = {}, t1[2] = {}, t2[2] = {}, st[2] = {}, so = 0;
     };
     std::vector<StreamSave> ssave;
     std::vector<char> has_ssave;
+};
+
+// The LN tensors of one s,t net with R residual blocks, numbered in the order of their [B][2] statistics
+// blocks (mean, rstd per image): the inputs of conv_a (y_r), conv_out (y_R), the grouped stage (t1_r) and
+// conv_b (t2_r). The training forward writes the statistics at these indices, the backward reads them.
+struct LnIndex {
+    int R = 0;
+    int ln1(int r) const { return r; }
+    int ln_out() const { return R; }
+    int ln2(int r) const { return R + 1 + r; }
+    int ln3(int r) const { return 2 * R + 1 + r; }
+    int count() const { return 3 * R + 1; }
+};
+
+// A streamed layer's activations at batch B, as the training forward leaves them for the backward (a
+// StreamSave) or as the backward recomputes them (the scratch set): per net y [R+1][B][HW][nk], the full
+// t1 [R][B][HW][nk], t2 [R][B][HW][gc], the LN statistics [LnIndex::count()][B][2] and the raw conv_out
+// [B][HW][dc2]. The *_f members are one slice's floats; the *_bytes() are the regions a StreamSave holds.
+struct StreamActs {
+    LnIndex ln;
+    size_t y_f = 0, t2_f = 0, so_f = 0, st_f = 0;
+    float *yb[2] = {}, *t1b[2] = {}, *t2b[2] = {}, *stb[2] = {}, *sob[2] = {};
+
+    StreamActs() = default;
+    StreamActs(int B, const Coupling& c)
+        : ln{c.R}, y_f((size_t)B * c.hc * c.wc * c.nk), t2_f((size_t)B * c.hc * c.wc * c.gc),
+          so_f((size_t)B * c.hc * c.wc * c.dc2), st_f((size_t)B * 2) {}
+    size_t y_bytes() const { return (size_t)(ln.R + 1) * y_f * 4; }
+    size_t t1_bytes() const { return (size_t)(ln.R > 1 ? ln.R : 1) * y_f * 4; }
+    size_t t2_bytes() const { return (size_t)(ln.R > 1 ? ln.R : 1) * t2_f * 4; }
+    size_t st_bytes() const { return (size_t)ln.count() * st_f * 4; }
+    size_t so_bytes() const { return 2 * so_f * 4; }   // both nets
+    size_t save_bytes() const { return 2 * (y_bytes() + t1_bytes() + t2_bytes() + st_bytes()) + so_bytes(); }
+
+    float* y(int n, int r) const { return yb[n] + (size_t)r * y_f; }
+    float* t1(int n, int r) const { return t1b[n] + (size_t)r * y_f; }
+    float* t2(int n, int r) const { return t2b[n] + (size_t)r * t2_f; }
+    float* stats(int n, int i) const { return stb[n] + (size_t)i * st_f; }
+    float* so(int n) const { return sob[n]; }
+
+    // the saved set s / the recompute scratch set of T, in workspace ws
+    static StreamActs saved(char* ws, const TrainLayout::StreamSave& s, int B, const Coupling& c) {
+        StreamActs a(B, c);
+        for (int n = 0; n < 2; n++) {
+            a.yb[n] = (float*)(ws + s.y[n]), a.t1b[n] = (float*)(ws + s.t1[n]), a.t2b[n] = (float*)(ws + s.t2[n]);
+            a.stb[n] = (float*)(ws + s.st[n]), a.sob[n] = (float*)(ws + s.so) + (size_t)n * a.so_f;
+        }
+        return a;
+    }
+    static StreamActs scratch(char* ws, const TrainLayout& T, int B, const Coupling& c) {
+        StreamActs a(B, c);
+        for (int n = 0; n < 2; n++) {
+            a.yb[n] = (float*)(ws + T.ys[n]), a.t1b[n] = (float*)(ws + T.t1s[n]), a.t2b[n] = (float*)(ws + T.t2s[n]);
+            a.stb[n] = (float*)(ws + T.stats[n]), a.sob[n] = (float*)(ws + T.so[n]);
+        }
+        return a;
+    }
 };
 
 struct Plan {
@@ -288,11 +344,16 @@ struct Plan {
     }
 };
 
-// cnf_train.cpp: dL/dparams of the NLL (loss scaled by inv_batch = 1 / global batch) into dparams,
-// from the coupling inputs saved by the training forward in `workspace`
+// cnf_train.cpp
+// the fused LDS backward's gradient-row length (the longer net's parameter range) and the layout of the
+// split backward's stored chain gradients, into a's row, gs_rb, g_t3, g_t2, g_in, gsave_img: the one
+// source for ldsbwd_setup and for the buffers train_layout sizes from them
+void ldsbwd_geom(const Coupling& c, LdsBwdArgs& a);
 // fused LDS-layer backward geometry of coupling c (LDS layout, strides, shape fields of a); returns the
-// LDS bytes, 0 when it does not fit (cnf_train.cpp)
+// LDS bytes, 0 when it does not fit
 size_t ldsbwd_setup(const Plan& p, const Coupling& c, LdsBwdArgs& a);
+// dL/dparams of the NLL (loss scaled by inv_batch = 1 / global batch) into dparams, from the coupling
+// inputs and activations saved by the training forward in `workspace`
 typedef void (*LayerDoneFn)(void* user, int coupling_index);
 void flow_backward(Plan& p, const float* params, const float* xy, const float* zy, void* workspace, int B,
                    float inv_batch, float* dparams, hipStream_t st, const float* count = nullptr,

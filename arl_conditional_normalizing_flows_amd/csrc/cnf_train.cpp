@@ -2,16 +2,19 @@
 // conv_cINN_make_model.py:1850-1880: tf.GradientTape over log_loss :1800-1848).
 //
 // Gradient of loss = -(mean_b(llz_b + lly_b) + mean_b(logdet_b)) with respect to the canonical
-// parameter vector. The forward (cnf_flow_forward_train) saves every coupling layer's input; the
-// backward walks the layer schedule in reverse:
+// parameter vector. The training forward (cnf_flow_forward_train) saves every coupling layer's input
+// and, by default, its activations; the backward walks the layer schedule in reverse:
 //   - layout layers (squeeze / factor-out / final restoration) are permutations: their gradient is
 //     the inverse map applied to dL/dv (the same index tables as cnf_flow_inverse);
-//   - a coupling layer recomputes both s,t networks from its saved input (activations of every
-//     residual block kept for this one layer), runs the coupling-law backward, then each network
-//     in reverse: conv weight gradients (k_wgrad + scatter through the dense map onto the
-//     canonical parameters, so the grouped-conv closure quirk and group boundaries come out
-//     exactly), data gradients (k_tconv with transposed weights), LayerNorm backward with the
-//     per-element gamma/beta gradients.
+//   - a k_net_lds layer runs the fused backward (k_lds_bwd, cnf_ldsbwd.hip) from its saved LdsSave
+//     blocks: coupling_backward_lds;
+//   - a streamed layer (and every layer under LDS_BWD=0) runs StreamedBwd: the coupling-law backward,
+//     then each s,t network in reverse from the activations the forward saved (StreamActs) — recomputed
+//     first when they were not (over the save budget, TRAIN_SCHED bit SCHED_RECOMPUTE, the lone-layer
+//     API). Per conv: the weight gradient (launch_wgrad* + a scatter through the dense map onto the
+//     canonical parameters, so the grouped-conv closure quirk and group boundaries come out exactly),
+//     the data gradient (launch_tconv with transposed weights), and the LayerNorm backward with the
+//     per-element gamma / beta gradients.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,27 +36,22 @@ void hchk(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// LN-on-load descriptor of a conv input
-struct LnIn {
-    const float* stats = nullptr;
-    const float* gamma = nullptr;
-    const float* beta = nullptr;
-    int act = 0;
-};
-
-// debug option TRAIN_ALT bit 32: zero dt1's gradient buffer before the grouped branches' data gradients
-// instead of masking the channels outside their windows in the LN2 backward
-bool ln2_mask() { return (opts().train_alt & 32) == 0; }
-
-// the LN backward's reduction in the producing data-gradient kernel (TRAIN_ALT bit 16: k_lnb_reduce)
-bool fused_lnr() { return (opts().train_alt & 16) == 0; }
-
 int wgrad_chunks(int B, int npx) {
     const long long total = (long long)B * npx;
     return (int)std::max<long long>(1, std::min<long long>(64, (total + 511) / 512));
 }
 
 }  // namespace
+
+void ldsbwd_geom(const Coupling& c, LdsBwdArgs& a) {
+    const int HW = c.hc * c.wc;
+    a.row = (int)std::max(c.net[0].hi - c.net[0].lo, c.net[1].hi - c.net[1].lo);
+    a.gs_rb = HW * (2 * c.nk + c.gc);
+    a.g_t3 = HW * c.nk;
+    a.g_t2 = HW * (c.nk + c.gc);
+    a.g_in = c.R * a.gs_rb;
+    a.gsave_img = (a.g_in + HW * c.nk + 3) / 4 * 4;
+}
 
 // LDS pixel stride for C channels: a multiple of 4 floats (16-byte quads), odd in quads
 static int bwd_stride(int C) {
@@ -137,12 +135,7 @@ size_t ldsbwd_setup(const Plan& p, const Coupling& c, LdsBwdArgs& a) {
     a.save_t1 = s.t1;
     a.save_t2 = s.t2;
     a.save_st = s.st;
-    a.row = (int)std::max(c.net[0].hi - c.net[0].lo, c.net[1].hi - c.net[1].lo);
-    a.gs_rb = HW * (2 * c.nk + c.gc);
-    a.g_t3 = HW * c.nk;
-    a.g_t2 = HW * (c.nk + c.gc);
-    a.g_in = c.R * a.gs_rb;
-    a.gsave_img = (a.g_in + HW * c.nk + 3) / 4 * 4;
+    ldsbwd_geom(c, a);
     return off;
 }
 
@@ -156,18 +149,20 @@ TrainLayout Plan::train_layout(int B) const {
         return o;
     };
     const size_t Bz = (size_t)B;
+    // the recompute scratch set holds any one layer's activations: per-image maxima over the layers
     int64_t m_y = 0, m_t1 = 0, m_t2 = 0, m_so = 0, m_nk = 0, m_gc = 0, m_u1 = 0, m_dense = 0, m_co = 0;
     int m_st = 1;
     for (const Coupling& c : couplings) {
         const int64_t npx = (int64_t)c.hc * c.wc;
-        m_y = std::max<int64_t>(m_y, (int64_t)(c.R + 1) * npx * c.nk);
-        m_t1 = std::max<int64_t>(m_t1, (int64_t)c.R * npx * c.nk);
-        m_t2 = std::max<int64_t>(m_t2, (int64_t)c.R * npx * c.gc);
-        m_so = std::max<int64_t>(m_so, npx * c.dc2);
+        const StreamActs a(1, c);
+        m_y = std::max<int64_t>(m_y, (int64_t)(c.R + 1) * a.y_f);
+        m_t1 = std::max<int64_t>(m_t1, (int64_t)c.R * a.y_f);
+        m_t2 = std::max<int64_t>(m_t2, (int64_t)c.R * a.t2_f);
+        m_so = std::max<int64_t>(m_so, a.so_f);
         m_nk = std::max<int64_t>(m_nk, npx * c.nk);
         m_gc = std::max<int64_t>(m_gc, npx * c.gc);
         m_u1 = std::max<int64_t>(m_u1, npx * c.dc1);
-        m_st = std::max(m_st, 3 * c.R + 1);
+        m_st = std::max(m_st, a.ln.count());
         m_dense = std::max<int64_t>(m_dense, 9LL * c.dc1 * c.nk);
         m_dense = std::max<int64_t>(m_dense, (int64_t)c.nk * c.nk);
         m_dense = std::max<int64_t>(m_dense, (int64_t)c.gc * c.nk);
@@ -223,152 +218,176 @@ TrainLayout Plan::train_layout(int B) const {
         const LdsSave s = LdsSave::of(HW, c.nk, c.gc, c.R);
         T.act_save[c.index] = take(2 * Bz * s.img * 4);
         T.so_save[c.index] = take(2 * Bz * HW * c.dc2 * 4);
-        T.row_max = std::max<int>(T.row_max, (int)std::max(c.net[0].hi - c.net[0].lo, c.net[1].hi - c.net[1].lo));
+        LdsBwdArgs g{};
+        ldsbwd_geom(c, g);
+        T.row_max = std::max(T.row_max, g.row);
+        T.gsave_max = std::max(T.gsave_max, g.gsave_img);
     }
     if (T.row_max > 0) {
         T.rows = take(2 * Bz * T.row_max * 4);
         T.rows2 = take(2 * Bz * T.row_max * 4);
-        for (const Coupling& c : couplings) {
-            if (!c.lds_bwd) continue;
-            const int HW = c.hc * c.wc;
-            T.gsave_max = std::max(T.gsave_max, ((c.R * (2 * c.nk + c.gc) + c.nk) * HW + 3) / 4 * 4);
-        }
         for (int par = 0; par < 2; par++) {
             T.gsave[par] = take(2 * Bz * T.gsave_max * 4);
             for (int n = 0; n < 2; n++) T.dso_l[par][n] = take(Bz * m_so * 4);
         }
     }
-    // streamed layers' saved activations, when all of them fit 16 GiB (TRAIN_SCHED bit 2: recompute)
+    // streamed layers' saved activations, when all of them fit 16 GiB (SCHED_RECOMPUTE: none)
     T.ssave.assign(couplings.size(), TrainLayout::StreamSave{});
     T.has_ssave.assign(couplings.size(), 0);
-    {
-        const bool on = (opts.train_sched & 2) == 0;
-        size_t need = 0;
+    auto saves = [](const Coupling& c) { return !c.use_lds && !c.t2_mapped; };
+    size_t need = 0;
+    for (const Coupling& c : couplings)
+        if (saves(c)) need += StreamActs(B, c).save_bytes();
+    if ((opts.train_sched & SCHED_RECOMPUTE) == 0 && need <= (16ull << 30))
         for (const Coupling& c : couplings) {
-            if (c.use_lds || c.t2_mapped) continue;
-            const size_t npx = (size_t)c.hc * c.wc;
-            need += 2 * Bz * npx * ((size_t)(c.R + 1) * c.nk + (size_t)c.R * c.nk + (size_t)c.R * c.gc + c.dc2) * 4;
-        }
-        if (on && need <= (16ull << 30))
-            for (const Coupling& c : couplings) {
-                if (c.use_lds || c.t2_mapped) continue;
-                const size_t npx = (size_t)c.hc * c.wc;
-                TrainLayout::StreamSave& s = T.ssave[c.index];
-                for (int n = 0; n < 2; n++) {
-                    s.y[n] = take((size_t)(c.R + 1) * Bz * npx * c.nk * 4);
-                    s.t1[n] = take((size_t)std::max(c.R, 1) * Bz * npx * c.nk * 4);
-                    s.t2[n] = take((size_t)std::max(c.R, 1) * Bz * npx * c.gc * 4);
-                    s.st[n] = take((size_t)(3 * c.R + 1) * Bz * 2 * 4);
-                }
-                s.so = take(2 * Bz * npx * c.dc2 * 4);
-                T.has_ssave[c.index] = 1;
+            if (!saves(c)) continue;
+            const StreamActs a(B, c);
+            TrainLayout::StreamSave& s = T.ssave[c.index];
+            for (int n = 0; n < 2; n++) {
+                s.y[n] = take(a.y_bytes());
+                s.t1[n] = take(a.t1_bytes());
+                s.t2[n] = take(a.t2_bytes());
+                s.st[n] = take(a.st_bytes());
             }
-    }
+            s.so = take(a.so_bytes());
+            T.has_ssave[c.index] = 1;
+        }
     T.total = off;
     return T;
 }
 
 namespace {
 
-struct TExec {
-    Plan& p;
-    const float* params;
+// One training call's view: Exec's plan, parameters, workspace and stream (no aux image: the training
+// kernels read the dense backward image bw), plus what only the backward has. Copied per net chain, so
+// it refers to the call's TrainLayout instead of holding one.
+struct TExec : Exec {
     float* dparams;
-    char* ws;
-    WsLayout L;
-    TrainLayout T;
-    int B;
-    hipStream_t st;
+    const TrainLayout& T;
     float inv_batch_ = 0.f;
     const float* count = nullptr;   // device global image count (overrides inv_batch_)
     bool saved = false;             // the training forward saved the streamed layers' activations (flow backward)
-    int net = 0;   // which per-net scratch set (and stream) this executor's launches use
-    hipStream_t wst = nullptr;   // weight-gradient stream (null: on st)
-    const float* bw() const { return reinterpret_cast<const float*>(ws + T.bw); }
-    template <class X>
-    X* at(size_t off) const {
-        return reinterpret_cast<X*>(ws + off);
-    }
+    int net = 0;                    // which per-net scratch set this executor's launches use
+    hipStream_t wst = nullptr;      // weight-gradient stream (null: on st)
+    const float* bw() const { return at<const float>(T.bw); }
+    const float* zeros() const { return at<const float>(T.zeros); }
+    double* lnsum() const { return at<double>(T.lnsum[net]); }
 };
 
-// out = conv(in) over the dense image of pc (forward, sgn = +1)
-void conv_fwd(TExec& E, int h, int w, const float* in, int in_cs, int in_off, int K, const LnIn& ln,
-              const PackedConv& pc, int cout, int dil, const float* res, float* out, int out_cs, int out_off) {
+// what both entry points do first: the executor, and on its stream the dense backward image, zeroed
+// parameter gradients and the zeros block
+TExec begin_backward(Plan& p, const TrainLayout& T, const float* params, float* dparams, void* workspace, int B,
+                     hipStream_t st) {
+    TExec E{{p, params, nullptr, (char*)workspace, p.layout(B), B, st}, dparams, T};
+    // pooled events: each record of this call gets its own (a re-recorded event that a queued wait still
+    // references serialised the two nets' chains on the GPU); the previous call's waits are all enqueued
+    p.tev_next = 0;
+    if (p.n_bw > 0) launch_pack(params, p.dev_bw_map, E.at<float>(T.bw), (long long)p.n_bw, st);
+    hchk(hipMemsetAsync(dparams, 0, (size_t)p.n_params * 4, st), "hipMemsetAsync");
+    hchk(hipMemsetAsync(E.at<float>(T.zeros), 0, 64 * 4, st), "hipMemsetAsync");
+    return E;
+}
+
+// ---- one convolution's three launches ------------------------------------------------------------------
+struct Geom {   // the (compressed) image every conv of a coupling layer runs on
+    int h, w;
+};
+
+// channels [off, off + c) of an NHWC tensor with cs floats per pixel (as cnf_coupling.cpp's Window)
+template <class T>
+struct Window {
+    T* ptr = nullptr;
+    int cs = 0, off = 0, c = 0;
+};
+using Src = Window<const float>;
+using Dst = Window<float>;
+template <class T>
+Window<T> whole(T* p, int c) {   // a dense tensor of c channels
+    return {p, c, 0, c};
+}
+template <class T>
+Window<T> branch_in(T* t1, int nk, const Branch& b) {   // what branch b reads of the nk-channel t1
+    return {t1, nk, b.cin_off, b.cin};
+}
+template <class T>
+Window<T> branch_out(T* t2, int gc, const Branch& b) {   // branch b's slice of the gc-channel concat t2
+    return {t2, gc, b.out_off, b.cout};
+}
+
+// LN-on-load descriptor of a conv input
+struct LnIn {
+    const float* stats = nullptr;
+    const float* gamma = nullptr;
+    const float* beta = nullptr;
+    int act = 0;
+};
+
+// the fields a convolution and its data gradient share: out = W * in over pc's dense image
+TConvArgs tconv_args(const TExec& E, Geom g, Src in, const PackedConv& pc, int dil, Dst out) {
     TConvArgs a{};
-    a.in = in;
-    a.in_cs = in_cs;
-    a.in_off = in_off;
-    a.K = K;
+    a.in = in.ptr;
+    a.in_cs = in.cs;
+    a.in_off = in.off;
+    a.K = in.c;
+    a.w = E.bw() + pc.dw;
+    a.wt = (long long)in.c * out.c;
+    a.out = out.ptr;
+    a.out_cs = out.cs;
+    a.out_off = out.off;
+    a.N = out.c;
+    a.H = g.h;
+    a.W = g.w;
+    a.taps = pc.taps;
+    a.dil = dil;
+    a.B = E.B;
+    a.zero = E.zeros();
+    return a;
+}
+
+// out = conv(LN(in)) (+ res) over the dense image of pc (forward, sgn = +1)
+void conv_fwd(TExec& E, Geom g, Src in, const LnIn& ln, const PackedConv& pc, int dil, Dst out,
+              const float* res = nullptr) {
+    TConvArgs a = tconv_args(E, g, in, pc, dil, out);
     a.stats = ln.stats;
     a.gamma = ln.gamma;
     a.beta = ln.beta;
     a.act = ln.act;
-    a.w = E.bw() + pc.dw;
-    a.wt = (long long)K * cout;
-    a.wk = cout;
+    a.wk = out.c;
     a.wn = 1;
     a.bias = E.bw() + pc.db;
     a.res = res;
-    a.out = out;
-    a.out_cs = out_cs;
-    a.out_off = out_off;
-    a.N = cout;
-    a.accumulate = 0;
-    a.H = h;
-    a.W = w;
-    a.taps = pc.taps;
-    a.dil = dil;
     a.sgn = 1;
-    a.B = E.B;
-    a.zero = E.at<float>(E.T.zeros);
     launch_tconv(a, E.st);
 }
 
-// dx (=|+=) conv^T(dy): dy has cout channels at (dy_cs, dy_off), dx gets cin channels at (dx_cs, dx_off)
-// With lr (an LN whose input has dx's layout and whose output gradient dx is), the kernel also writes the
-// LN backward's per-image reduction partials to the net's lnsum; returns their count per image (0: not
-// fused — ln_bwd runs k_lnb_reduce)
+// an LN whose input has dx's layout and whose output gradient dx is: conv_dgrad's kernel also writes
+// that LN backward's per-image reduction partials to the net's lnsum
 struct LnRed {
     const float* x = nullptr;
     const float* gamma = nullptr;
     const float* stats = nullptr;
     int base = 0;   // this launch's first partial (several launches that write disjoint windows share one LN)
 };
-int conv_dgrad(TExec& E, int h, int w, const float* dy, int dy_cs, int dy_off, int cout, const PackedConv& pc, int cin,
-               int dil, float* dx, int dx_cs, int dx_off, int accumulate, const LnRed* lr = nullptr) {
-    TConvArgs a{};
-    if (lr != nullptr && lr->stats != nullptr && fused_lnr()) {
+// dx (=|+=) conv^T(dy); returns the partials per image written for lr (0: not fused — ln_bwd runs
+// k_lnb_reduce, as it always does under ALT_LNB_REDUCE)
+int conv_dgrad(TExec& E, Geom g, Src dy, const PackedConv& pc, int dil, Dst dx, int accumulate,
+               const LnRed* lr = nullptr) {
+    TConvArgs a = tconv_args(E, g, dy, pc, dil, dx);
+    if (lr != nullptr && lr->stats != nullptr && (opts().train_alt & ALT_LNB_REDUCE) == 0) {
         a.lnr_x = lr->x;
         a.lnr_gamma = lr->gamma;
         a.lnr_stats = lr->stats;
-        a.lnr_part = E.at<double>(E.T.lnsum[E.net]);
+        a.lnr_part = E.lnsum();
         a.lnr_base = lr->base;
         a.lnr_stride = LNR_MAXPARTS;
     }
-    a.in = dy;
-    a.in_cs = dy_cs;
-    a.in_off = dy_off;
-    a.K = cout;
-    a.w = E.bw() + pc.dw;
-    a.wt = (long long)cin * cout;
     a.wk = 1;
-    a.wn = cout;
-    a.out = dx;
-    a.out_cs = dx_cs;
-    a.out_off = dx_off;
-    a.N = cin;
+    a.wn = dy.c;
     a.accumulate = accumulate;
-    a.H = h;
-    a.W = w;
-    a.taps = pc.taps;
-    a.dil = dil;
     a.sgn = -1;
-    a.B = E.B;
-    a.zero = E.at<float>(E.T.zeros);
     return launch_tconv(a, E.st);
 }
 
-// dW, db of a conv: X (cin channels at x_cs/x_off, LN-on-load) and dY (cout at dy_cs/dy_off)
 hipEvent_t tevent(Plan& p) {
     constexpr int flags = (int)hipEventDisableTiming;
     if (p.tev_next == p.tev.size()) {
@@ -379,91 +398,87 @@ hipEvent_t tevent(Plan& p) {
     return p.tev[p.tev_next++];
 }
 
-// dW, db of a conv (below) on E's weight-gradient stream when it has one: it waits for the chain's
-// launches so far (its X and dY are ready) and returns the event of its completion, which the chain
-// waits for before it overwrites that dY buffer
-hipEvent_t conv_wgrad_impl(TExec& E, int h, int w, const float* x, int x_cs, int x_off, int cin, const LnIn& ln,
-                           const float* dy, int dy_cs, int dy_off, int cout, const PackedConv& pc, int dil);
-hipEvent_t conv_wgrad(TExec& E, int h, int w, const float* x, int x_cs, int x_off, int cin, const LnIn& ln,
-                      const float* dy, int dy_cs, int dy_off, int cout, const PackedConv& pc, int dil) {
+WGradArgs wgrad_args(const TExec& E, Geom g, Src x, const LnIn& ln, Src dy, const PackedConv& pc, int dil) {
+    WGradArgs a{};
+    a.x = x.ptr;
+    a.x_cs = x.cs;
+    a.x_off = x.off;
+    a.CI = x.c;
+    a.stats = ln.stats;
+    a.gamma = ln.gamma;
+    a.beta = ln.beta;
+    a.act = ln.act;
+    a.dy = dy.ptr;
+    a.dy_cs = dy.cs;
+    a.dy_off = dy.off;
+    a.CO = dy.c;
+    a.part = E.at<float>(E.T.wpart[E.net]);
+    a.bpart = E.at<float>(E.T.bpart[E.net]);
+    a.H = g.h;
+    a.W = g.w;
+    a.taps = pc.taps;
+    a.dil = dil;
+    a.B = E.B;
+    return a;
+}
+
+// dW, db of a conv on stream st: the kernel its shape allows, then the scatter of its partial rows
+// through the dense map onto the canonical parameters
+void wgrad_launch(const TExec& E, WGradArgs a, const PackedConv& pc, hipStream_t st) {
+    const int h = a.H, w = a.W, cin = a.CI, cout = a.CO;
+    const int64_t* map = E.p.dev_bw_map;
+    const long long nw = (long long)pc.taps * cin * cout;
+    if (train_valu_kernels() || !wgrad_band_ok(h, w, pc.taps, a.dil, cin, cout)) {
+        a.chunks = wgrad_chunks(E.B, h * w);
+        const long long total = (long long)E.B * h * w;
+        a.chunk_px = (int)(((total + a.chunks - 1) / a.chunks + 15) / 16 * 16);
+        launch_wgrad(a, st);
+        launch_grad_scatter(a.part, a.chunks, nw, map + pc.dw, E.dparams, st);
+        launch_grad_scatter(a.bpart, a.chunks, cout, map + pc.db, E.dparams, st);
+        return;
+    }
+    // thin outputs (the streamed conv_out, CO = dc2): k_wgrad_thin, rows of [weights | bias] as below
+    if ((long long)h * w * a.x_cs * 4 < (1LL << 31) && wgrad_thin_ok(h, w, pc.taps, a.dil, cin, cout) &&
+        pc.db == pc.dw + nw) {
+        a.chunks = wgrad_thin_chunks(E.B, h, w);
+        launch_wgrad_thin(a, st);
+        launch_grad_scatter(a.part, a.chunks, nw + cout, map + pc.dw, E.dparams, st);
+        return;
+    }
+    // k_wgrad_direct (ALT_WGRAD_BAND: k_wgrad_band): rows of [weights | bias]; the dense image keeps the
+    // bias right after the weights (pc.db == pc.dw + taps * cin * cout), so one scatter reduces both
+    if ((opts().train_alt & ALT_WGRAD_BAND) == 0 && wgrad_direct_ok(h, w, pc.taps)) {
+        a.chunks = wgrad_direct_chunks(E.B, h);
+        a.chunk_px = -1;
+        a.zero = E.zeros();
+    } else {
+        a.chunks = wgrad_band_chunks(E.B, h, w, pc.taps, cin, cout);
+    }
+    launch_wgrad(a, st);
+    if (pc.db != pc.dw + nw) throw std::logic_error("dense image: bias not after the weights");
+    launch_grad_scatter(a.part, a.chunks, nw + cout, map + pc.dw, E.dparams, st);
+}
+
+// dW, db of a conv from X (LN-on-load) and dY, on E's weight-gradient stream when it has one: there it
+// waits for the chain's launches so far (its X and dY are ready) and returns the event of its completion
+// (null on the chain's own stream, where order alone protects dY)
+hipEvent_t conv_wgrad(TExec& E, Geom g, Src x, const LnIn& ln, Src dy, const PackedConv& pc, int dil) {
+    const WGradArgs a = wgrad_args(E, g, x, ln, dy, pc, dil);
     if (E.wst == nullptr) {
-        conv_wgrad_impl(E, h, w, x, x_cs, x_off, cin, ln, dy, dy_cs, dy_off, cout, pc, dil);
+        wgrad_launch(E, a, pc, E.st);
         return nullptr;
     }
     hipEvent_t in = tevent(E.p), done = tevent(E.p);
     hchk(hipEventRecord(in, E.st), "hipEventRecord");
     hchk(hipStreamWaitEvent(E.wst, in, 0), "hipStreamWaitEvent");
-    TExec G = E;
-    G.st = E.wst;
-    conv_wgrad_impl(G, h, w, x, x_cs, x_off, cin, ln, dy, dy_cs, dy_off, cout, pc, dil);
+    wgrad_launch(E, a, pc, E.wst);
     hchk(hipEventRecord(done, E.wst), "hipEventRecord");
     return done;
 }
 
-void chain_wait(TExec& E, hipEvent_t done) {
-    if (done != nullptr) hchk(hipStreamWaitEvent(E.st, done, 0), "hipStreamWaitEvent");
-}
-
-hipEvent_t conv_wgrad_impl(TExec& E, int h, int w, const float* x, int x_cs, int x_off, int cin, const LnIn& ln,
-                           const float* dy, int dy_cs, int dy_off, int cout, const PackedConv& pc, int dil) {
-    WGradArgs a{};
-    a.x = x;
-    a.x_cs = x_cs;
-    a.x_off = x_off;
-    a.CI = cin;
-    a.stats = ln.stats;
-    a.gamma = ln.gamma;
-    a.beta = ln.beta;
-    a.act = ln.act;
-    a.dy = dy;
-    a.dy_cs = dy_cs;
-    a.dy_off = dy_off;
-    a.CO = cout;
-    a.part = E.at<float>(E.T.wpart[E.net]);
-    a.bpart = E.at<float>(E.T.bpart[E.net]);
-    a.H = h;
-    a.W = w;
-    a.taps = pc.taps;
-    a.dil = dil;
-    a.B = E.B;
-    const int64_t* map = E.p.dev_bw_map;
-    const long long nw = (long long)pc.taps * cin * cout;
-    if (train_valu_kernels() || !wgrad_band_ok(h, w, pc.taps, dil, cin, cout)) {
-        a.chunks = wgrad_chunks(E.B, h * w);
-        const long long total = (long long)E.B * h * w;
-        a.chunk_px = (int)(((total + a.chunks - 1) / a.chunks + 15) / 16 * 16);
-        launch_wgrad(a, E.st);
-        launch_grad_scatter(a.part, a.chunks, nw, map + pc.dw, E.dparams, E.st);
-        launch_grad_scatter(a.bpart, a.chunks, cout, map + pc.db, E.dparams, E.st);
-        return nullptr;
-    }
-    // thin outputs (the streamed conv_out, CO = dc2): k_wgrad_thin, rows of [weights | bias] as below
-    if ((long long)h * w * x_cs * 4 < (1LL << 31) && wgrad_thin_ok(h, w, pc.taps, dil, cin, cout) && pc.db == pc.dw + nw) {
-        a.chunks = wgrad_thin_chunks(E.B, h, w);
-        launch_wgrad_thin(a, E.st);
-        launch_grad_scatter(a.part, a.chunks, nw + cout, map + pc.dw, E.dparams, E.st);
-        return nullptr;
-    }
-    // k_wgrad_direct (k_wgrad_band with TRAIN_ALT bit 2): rows of [weights | bias]; the dense image
-    // keeps the bias right after the weights (pc.db == pc.dw + taps * cin * cout), so one scatter
-    // reduces both
-    const bool direct = (opts().train_alt & 2) == 0;
-    if (direct && wgrad_direct_ok(h, w, pc.taps)) {
-        a.chunks = wgrad_direct_chunks(E.B, h);
-        a.chunk_px = -1;
-        a.zero = E.at<float>(E.T.zeros);
-    } else {
-        a.chunks = wgrad_band_chunks(E.B, h, w, pc.taps, cin, cout);
-    }
-    launch_wgrad(a, E.st);
-    if (pc.db != pc.dw + nw) throw std::logic_error("dense image: bias not after the weights");
-    launch_grad_scatter(a.part, a.chunks, nw + cout, map + pc.dw, E.dparams, E.st);
-    return nullptr;
-}
-
 void ln_bwd(TExec& E, const float* x, const float* dxo, const LnIn& ln, long long n, float* dx, int accumulate,
             int64_t g_off, int64_t b_off, int presum = 0, unsigned long long cmask = 0, int cmod = 0) {
-    launch_ln_backward(x, dxo, ln.gamma, ln.stats, E.at<double>(E.T.lnsum[E.net]), n, E.B, 1, dx, accumulate,
+    launch_ln_backward(x, dxo, ln.gamma, ln.stats, E.lnsum(), n, E.B, 1, dx, accumulate,
                        ln.stats ? E.dparams + g_off : nullptr, ln.stats ? E.dparams + b_off : nullptr,
                        E.at<float>(E.T.lnpart[E.net]), E.st, presum, LNR_MAXPARTS, cmask, cmod);
 }
@@ -497,13 +512,42 @@ void stream_wait(hipStream_t from, hipStream_t to, hipEvent_t ev) {
     hchk(hipStreamWaitEvent(to, ev, 0), "hipStreamWaitEvent");
 }
 
-// One coupling layer's backward (conv_cINN_make_model.py:1850-1880 through the layer): the two s,t
-// nets are independent until the coupling law joins them, so net b's recompute and backward chain run
-// on the plan's side stream (its own scratch set) while net A's run on the caller's stream: the many
-// small, latency-bound launches of the two chains overlap.
-// the fused backward of a k_net_lds layer (cnf_ldsbwd.hip) from the activations the training forward
-// saved: coupling law backward, one k_lds_bwd launch for both nets, the batch sum of the gradient rows
-// the fused backward of a k_net_lds layer (cnf_ldsbwd.hip) from the activations the training forward
+// coupling law backward at u for upstream dv: du (u2 part, u1 copy), dL/d s_pre, dL/dt, and dL/d tanh_w
+// (per-workgroup partials, then their sum)
+void coupling_law_backward(TExec& E, const Coupling& c, const float* u, const float* dv, float* du,
+                           const float* s_pre, float* ds_pre, float* dt) {
+    CoupBwArgs a{};
+    a.u = u;
+    a.dv = dv;
+    a.s_pre = s_pre;
+    a.tanh_w = E.params + c.net[0].tanh_w;
+    a.du = du;
+    a.ds_pre = ds_pre;
+    a.dt = dt;
+    a.dw_part = E.at<double>(E.T.dwpart);
+    a.g_ld = -E.inv_batch_;
+    a.count = E.count;
+    a.H = c.H;
+    a.W = c.W;
+    a.D = c.D;
+    a.mask = c.mask;
+    a.mask_c = c.mask_c;
+    a.hc = c.hc;
+    a.wc = c.wc;
+    a.dc1 = c.dc1;
+    a.dc2 = c.dc2;
+    const int np = std::max(1, E.L.ld_parts);
+    launch_coupling_backward(a, E.B, np, E.st);
+    launch_dsum(a.dw_part, (long long)E.B * np, E.dparams + c.net[0].tanh_w, E.st);
+}
+
+// du += the two nets' u1 gradients, net A's first (fixed order: bitwise reproducible)
+void scatter_du1c(TExec& E, const Coupling& c, float* du, hipStream_t st) {
+    for (int n = 0; n < 2; n++)
+        launch_scatter_add_u1c(E.at<float>(E.T.du1c[n]), du, E.B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, st);
+}
+
+// The fused backward of a k_net_lds layer (cnf_ldsbwd.hip) from the activations the training forward
 // saved: coupling law backward, k_lds_bwd for both nets, the batch sum of the gradient rows. Split
 // (par >= 0): the data-gradient chain (k_lds_bwd mode 1, storing the gradients the weight gradients
 // need) on the caller's stream, then the weight gradients (mode 2) and the row sum on the side stream
@@ -512,36 +556,10 @@ void stream_wait(hipStream_t from, hipStream_t to, hipEvent_t ev) {
 // gradients complete), null unsplit. par selects the alternating buffer set.
 hipEvent_t coupling_backward_lds(TExec& E, const Coupling& c, const float* u, const float* dv, float* du, int par) {
     const int B = E.B;
-    const float* P = E.params;
     const bool split = par >= 0;
-    const float* so0 = E.at<float>(E.T.so_save[c.index]);
     float* dso0 = E.at<float>(split ? E.T.dso_l[par][0] : E.T.dso[0]);
     float* dso1 = E.at<float>(split ? E.T.dso_l[par][1] : E.T.dso[1]);
-    {
-        CoupBwArgs a{};
-        a.u = u;
-        a.dv = dv;
-        a.s_pre = so0;
-        a.tanh_w = P + c.net[0].tanh_w;
-        a.du = du;
-        a.ds_pre = dso0;
-        a.dt = dso1;
-        a.dw_part = E.at<double>(E.T.dwpart);
-        a.g_ld = -E.inv_batch_;
-        a.count = E.count;
-        a.H = c.H;
-        a.W = c.W;
-        a.D = c.D;
-        a.mask = c.mask;
-        a.mask_c = c.mask_c;
-        a.hc = c.hc;
-        a.wc = c.wc;
-        a.dc1 = c.dc1;
-        a.dc2 = c.dc2;
-        const int np = std::max(1, E.L.ld_parts);
-        launch_coupling_backward(a, B, np, E.st);
-        launch_dsum(a.dw_part, (long long)B * np, E.dparams + c.net[0].tanh_w, E.st);
-    }
+    coupling_law_backward(E, c, u, dv, du, E.at<float>(E.T.so_save[c.index]), dso0, dso1);
     LdsBwdArgs a;
     if (ldsbwd_setup(E.p, c, a) == 0) throw std::logic_error("fused LDS backward planned for a layer it does not fit");
     a.save = E.at<float>(E.T.act_save[c.index]);
@@ -550,7 +568,7 @@ hipEvent_t coupling_backward_lds(TExec& E, const Coupling& c, const float* u, co
     a.u = u;
     a.du1c[0] = E.at<float>(E.T.du1c[0]);
     a.du1c[1] = E.at<float>(E.T.du1c[1]);
-    a.params = P;
+    a.params = E.params;
     a.bw = E.bw();
     a.bw_map = E.p.dev_bw_map;
     a.offs = E.p.dev_table + c.dev_bwd_offs;
@@ -571,16 +589,14 @@ hipEvent_t coupling_backward_lds(TExec& E, const Coupling& c, const float* u, co
         a.mode = 0;
         launch_lds_bwd(a, B, E.st);
         launch_grad_rows(a.part, B, a.row, n0.lo, n1.lo, (int)(n0.hi - n0.lo), (int)(n1.hi - n1.lo), E.dparams, E.st);
-        launch_scatter_add_u1c(a.du1c[0], du, B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, E.st);
-        launch_scatter_add_u1c(a.du1c[1], du, B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, E.st);
+        scatter_du1c(E, c, du, E.st);
         return nullptr;
     }
     ensure_side(E.p);
     a.gsave = E.at<float>(E.T.gsave[par]);
     a.mode = 1;
     launch_lds_bwd(a, B, E.st);
-    launch_scatter_add_u1c(a.du1c[0], du, B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, E.st);
-    launch_scatter_add_u1c(a.du1c[1], du, B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, E.st);
+    scatter_du1c(E, c, du, E.st);
     hipStream_t ws = E.p.wside[1];
     stream_wait(E.st, ws, tevent(E.p));   // the chain's stored gradients and LN rows
     a.mode = 2;
@@ -592,216 +608,252 @@ hipEvent_t coupling_backward_lds(TExec& E, const Coupling& c, const float* u, co
     return done;
 }
 
-void coupling_backward(TExec& E, const Coupling& c, const float* u, const float* dv, float* du) {
-    const int B = E.B, h = c.hc, w = c.wc, nk = c.nk, gc = c.gc, R = c.R;
-    const int64_t npx = (int64_t)h * w;
-    const bool ln = E.p.desc.layer_norm != 0;
-    const float* P = E.params;
-    ensure_side(E.p);
-    const bool wstreams = (opts().train_sched & 1) == 0;   // TRAIN_SCHED bit 1: weight gradients on the chain streams
-    TExec E0 = E;
-    E0.wst = wstreams ? E.p.wside[0] : nullptr;
-    TExec E1 = E;
-    E1.net = 1;
-    E1.st = E.p.side;
-    E1.wst = wstreams ? E.p.wside[1] : nullptr;
-    TExec* X[2] = {&E0, &E1};
-    float* u1c = E.at<float>(E.T.u1c);
-    launch_gather_u1c(u, u1c, B, c.H, c.W, c.D, c.mask, h, w, c.dc1, E.st);
-    // activations of both nets: y_r (r = 0..R), t1_r, t2_r; LN stats st[0..R] (y), st[R+1+r] (t1),
-    // st[2R+1+r] (t2), each [B][2]
-    // the training forward's saved activations of this (streamed) layer, when it saved them (the backward
-    // of a lone layer, cnf_coupling_backward, always recomputes)
-    const bool saved = E.saved && E.T.has_ssave[c.index];
-    const TrainLayout::StreamSave& SS = E.T.ssave[c.index];
-    auto Y = [&](int n, int r) { return E.at<float>(saved ? SS.y[n] : E.T.ys[n]) + (size_t)r * B * npx * nk; };
-    auto T1 = [&](int n, int r) { return E.at<float>(saved ? SS.t1[n] : E.T.t1s[n]) + (size_t)r * B * npx * nk; };
-    auto T2 = [&](int n, int r) { return E.at<float>(saved ? SS.t2[n] : E.T.t2s[n]) + (size_t)r * B * npx * gc; };
-    auto ST = [&](int n, int i) { return E.at<float>(saved ? SS.st[n] : E.T.stats[n]) + (size_t)i * B * 2; };
-    auto SO = [&](int n) { return saved ? E.at<float>(SS.so) + (size_t)n * B * npx * c.dc2 : E.at<float>(E.T.so[n]); };
-    auto lnin = [&](int n, int i, int64_t g, int64_t b) {
+// How the grouped stage's data gradients and the LN2 backward share dbuf, from the branches' input
+// windows alone. Pairwise disjoint windows (the reference group mode's closure windows [(card - 1) w,
+// card w) of each branch width w): every element of dbuf is final after the one launch that writes it,
+// so the LN2 reduction rides on those launches, each adding its window's partials after the previous
+// ones'. Disjoint over <= 64 channels (and not ALT_ZERO_DT1): the branches store their windows without
+// accumulating and the LN2 backward reads the channels outside `mask` as 0, so dbuf is not zeroed first.
+struct BranchWindows {
+    bool disjoint = true, masked = false;
+    unsigned long long mask = 0;
+};
+BranchWindows branch_windows(const Coupling& c) {
+    BranchWindows bw;
+    const int nb = (int)c.br.size();
+    for (int i = 0; i < nb; i++) {
+        for (int j = i + 1; j < nb; j++)
+            bw.disjoint = bw.disjoint && (c.br[i].cin_off + c.br[i].cin <= c.br[j].cin_off ||
+                                          c.br[j].cin_off + c.br[j].cin <= c.br[i].cin_off);
+        for (int ch = c.br[i].cin_off; ch < c.br[i].cin_off + c.br[i].cin && ch < 64; ch++) bw.mask |= 1ull << ch;
+    }
+    bw.masked = bw.disjoint && c.nk <= 64 && (opts().train_alt & ALT_ZERO_DT1) == 0;
+    return bw;
+}
+
+// One streamed coupling layer's backward (conv_cINN_make_model.py:1850-1880 through the layer). The two
+// s,t nets are independent until the coupling law joins them, so net b's chain (and recompute) runs on
+// the plan's side stream with its own scratch set while net A's runs on the caller's: the many small,
+// latency-bound launches of the two chains overlap. Each net's weight gradients run behind its chain on
+// a stream of their own (SCHED_WGRAD_ON_CHAIN: on the chain's).
+struct StreamedBwd {
+    struct Step {   // one stage of a net's chain: (this->*stage)(net, r)
+        void (StreamedBwd::*stage)(int, int);
+        int r;
+    };
+    // Buffer reuse. A chain's dY buffers are written once per residual block, and the weight gradient
+    // that reads one runs on another stream: wgrad() notes its completion event in the buffer, and the
+    // stage that next overwrites the buffer takes it through fresh(), which makes the chain wait for that
+    // reader first — dt2: conv_b's LN3 backward (read by the block after's branches), dt1: the LN2
+    // backward (read by the block after's conv_a), dy: conv_a's LN1 backward (read by this block's conv_b).
+    struct DyBuf {
+        float* p = nullptr;
+        hipEvent_t reader = nullptr;
+    };
+    struct Scratch {
+        DyBuf dy, dt1, dt2;
+        float *dln, *dbuf, *dcb, *du1c, *dso;
+    };
+
+    const Coupling& c;
+    TExec X[2];   // per net: its chain stream, weight-gradient stream and scratch set
+    const bool ln;
+    const float* const P;
+    const Geom g;
+    const long long n_nk, n_gc;   // elements per image of an nk- / gc-channel tensor
+    const bool saved;             // the forward saved this layer's activations (else: recompute)
+    const StreamActs A;
+    const BranchWindows bwin;
+    float* const u1c;
+    Scratch S[2];
+
+    StreamedBwd(TExec& E, const Coupling& c_)
+        : c(c_), X{E, E}, ln(E.p.desc.layer_norm != 0), P(E.params), g{c_.hc, c_.wc},
+          n_nk((long long)c_.hc * c_.wc * c_.nk), n_gc((long long)c_.hc * c_.wc * c_.gc),
+          saved(E.saved && E.T.has_ssave[c_.index]),
+          A(saved ? StreamActs::saved(E.ws, E.T.ssave[c_.index], E.B, c_) : StreamActs::scratch(E.ws, E.T, E.B, c_)),
+          bwin(branch_windows(c_)), u1c(E.at<float>(E.T.u1c)) {
+        ensure_side(E.p);
+        const bool wstreams = (opts().train_sched & SCHED_WGRAD_ON_CHAIN) == 0;
+        X[1].net = 1;
+        X[1].st = E.p.side;
+        for (int n = 0; n < 2; n++) {
+            X[n].wst = wstreams ? E.p.wside[n] : nullptr;
+            const TrainLayout& T = E.T;
+            S[n] = Scratch{{E.at<float>(T.dy[n])}, {E.at<float>(T.dt1[n])}, {E.at<float>(T.dt2[n])},
+                           E.at<float>(T.dln[n]), E.at<float>(T.dbuf[n]), E.at<float>(T.dc[n]),
+                           E.at<float>(T.du1c[n]), E.at<float>(T.dso[n])};
+        }
+    }
+
+    LnIn lnin(int n, int i, int64_t gamma, int64_t beta) const {
         LnIn l;
         l.act = 1;
         if (ln) {
-            l.stats = ST(n, i);
-            l.gamma = P + g;
-            l.beta = P + b;
+            l.stats = A.stats(n, i);
+            l.gamma = P + gamma;
+            l.beta = P + beta;
         }
         return l;
-    };
-    const LnIn raw{};
-    stream_wait(E.st, E1.st, tevent(E.p));   // u1c gathered
-    for (int n = 0; n < 2 && !saved; n++) {
-        TExec& En = *X[n];
+    }
+    void wgrad(int n, Src x, const LnIn& l, DyBuf& dy, Src dyw, const PackedConv& pc, int dil = 1) {
+        dy.reader = conv_wgrad(X[n], g, x, l, dyw, pc, dil);
+    }
+    float* fresh(int n, const DyBuf& b) {
+        if (b.reader != nullptr) hchk(hipStreamWaitEvent(X[n].st, b.reader, 0), "hipStreamWaitEvent");
+        return b.p;
+    }
+
+    // net n's activations again, from the gathered u1c
+    void recompute(int n) {
+        TExec& E = X[n];
         const NetParams& np = c.net[n];
-        conv_fwd(En, h, w, u1c, c.dc1, 0, c.dc1, raw, np.ci, nk, 1, nullptr, Y(n, 0), nk, 0);
-        if (ln) launch_ln_stats(Y(n, 0), npx * nk, B, 1, ST(n, 0), En.st);
-        for (int r = 0; r < R; r++) {
+        const int nk = c.nk, gc = c.gc, B = E.B;
+        auto stats = [&](const float* x, long long per_image, int i) {
+            if (ln) launch_ln_stats(x, per_image, B, 1, A.stats(n, i), E.st);
+        };
+        conv_fwd(E, g, whole<const float>(u1c, c.dc1), LnIn{}, np.ci, 1, whole(A.y(n, 0), nk));
+        stats(A.y(n, 0), n_nk, A.ln.ln1(0));
+        for (int r = 0; r < c.R; r++) {
             const RBParams& rb = np.rb[r];
-            conv_fwd(En, h, w, Y(n, r), nk, 0, nk, lnin(n, r, rb.ln1g, rb.ln1b), rb.ca, nk, 1, nullptr, T1(n, r), nk, 0);
-            if (ln) launch_ln_stats(T1(n, r), npx * nk, B, 1, ST(n, R + 1 + r), En.st);
+            conv_fwd(E, g, whole<const float>(A.y(n, r), nk), lnin(n, A.ln.ln1(r), rb.ln1g, rb.ln1b), rb.ca, 1,
+                     whole(A.t1(n, r), nk));
+            stats(A.t1(n, r), n_nk, A.ln.ln2(r));
             for (size_t bi = 0; bi < c.br.size(); bi++) {
                 const Branch& b = c.br[bi];
-                conv_fwd(En, h, w, T1(n, r), nk, b.cin_off, b.cin, lnin(n, R + 1 + r, rb.ln2g, rb.ln2b), rb.gc[bi],
-                         b.cout, b.dil, nullptr, T2(n, r), gc, b.out_off);
+                conv_fwd(E, g, branch_in<const float>(A.t1(n, r), nk, b), lnin(n, A.ln.ln2(r), rb.ln2g, rb.ln2b),
+                         rb.gc[bi], b.dil, branch_out(A.t2(n, r), gc, b));
             }
-            if (ln) launch_ln_stats(T2(n, r), npx * gc, B, 1, ST(n, 2 * R + 1 + r), En.st);
-            conv_fwd(En, h, w, T2(n, r), gc, 0, gc, lnin(n, 2 * R + 1 + r, rb.ln3g, rb.ln3b), rb.cb, nk, 1, Y(n, r),
-                     Y(n, r + 1), nk, 0);
-            if (ln) launch_ln_stats(Y(n, r + 1), npx * nk, B, 1, ST(n, r + 1), En.st);
+            stats(A.t2(n, r), n_gc, A.ln.ln3(r));
+            conv_fwd(E, g, whole<const float>(A.t2(n, r), gc), lnin(n, A.ln.ln3(r), rb.ln3g, rb.ln3b), rb.cb, 1,
+                     whole(A.y(n, r + 1), nk), A.y(n, r));
+            stats(A.y(n, r + 1), n_nk, A.ln.ln1(r + 1));
         }
-        conv_fwd(En, h, w, Y(n, R), nk, 0, nk, lnin(n, R, np.ln_out_g, np.ln_out_b), np.co, c.dc2, 1, nullptr,
-                 SO(n), c.dc2, 0);
+        conv_fwd(E, g, whole<const float>(A.y(n, c.R), nk), lnin(n, A.ln.ln_out(), np.ln_out_g, np.ln_out_b), np.co, 1,
+                 whole(A.so(n), c.dc2));
     }
-    stream_wait(E1.st, E.st, tevent(E.p));   // both nets' outputs
+
     // coupling law backward -> du (u2 part, u1 copy), dL/d s_pre, dL/dt, dL/dw
-    {
-        CoupBwArgs a{};
-        a.u = u;
-        a.dv = dv;
-        a.s_pre = SO(0);
-        a.tanh_w = P + c.net[0].tanh_w;
-        a.du = du;
-        a.ds_pre = E.at<float>(E.T.dso[0]);
-        a.dt = E.at<float>(E.T.dso[1]);
-        a.dw_part = E.at<double>(E.T.dwpart);
-        a.g_ld = -E.inv_batch_;
-        a.count = E.count;
-        a.H = c.H;
-        a.W = c.W;
-        a.D = c.D;
-        a.mask = c.mask;
-        a.mask_c = c.mask_c;
-        a.hc = h;
-        a.wc = w;
-        a.dc1 = c.dc1;
-        a.dc2 = c.dc2;
-        const int np = std::max(1, E.L.ld_parts);
-        launch_coupling_backward(a, B, np, E.st);
-        launch_dsum(a.dw_part, (long long)B * np, E.dparams + c.net[0].tanh_w, E.st);
+    void law(const float* u, const float* dv, float* du) {
+        coupling_law_backward(X[0], c, u, dv, du, A.so(0), S[0].dso, S[1].dso);
     }
-    stream_wait(E.st, E1.st, tevent(E.p));   // dL/d s_pre, dL/dt
-    // The two chains are enqueued interleaved, phase by phase (conv_out; per residual block conv_b + LN3,
-    // the branches + LN2, conv_a + LN1; conv_in): the GPU starts a stream's kernels in about the order
-    // the host submitted them across streams (measured: no kernel ran more than ~15 submissions ahead of
-    // the newest finished one), so a chain enqueued whole after the other only overlapped it at the end.
-    // Debug option TRAIN_SCHED bit 4 enqueues net A's chain, then net b's.
-    const bool interleave = (opts().train_sched & 4) == 0;
-    hipEvent_t ev_gc[2] = {nullptr, nullptr}, ev_ca[2] = {nullptr, nullptr}, ev_cb[2] = {nullptr, nullptr};
-    // phase k of net n: 0 conv_out + LN_out; 1 + 3j + {0, 1, 2} residual block r = R - 1 - j: conv_b + LN3,
-    // the grouped branches + LN2, conv_a + LN1; 1 + 3R conv_in
-    auto phase = [&](int n, int k) {
-        TExec& En = *X[n];
-        float* dy = E.at<float>(E.T.dy[n]);
-        float* dln = E.at<float>(E.T.dln[n]);
-        float* dbuf = E.at<float>(E.T.dbuf[n]);
-        float* dt1 = E.at<float>(E.T.dt1[n]);
-        float* dcb = E.at<float>(E.T.dc[n]);
-        float* dt2 = E.at<float>(E.T.dt2[n]);
-        float* du1c = E.at<float>(E.T.du1c[n]);
+
+    void conv_out(int n, int = 0) {
+        Scratch& s = S[n];
         const NetParams& np = c.net[n];
-        if (k == 0) {
-            const float* dso = E.at<float>(E.T.dso[n]);
-            const LnIn lo = lnin(n, R, np.ln_out_g, np.ln_out_b);
-            conv_wgrad(En, h, w, Y(n, R), nk, 0, nk, lo, dso, c.dc2, 0, c.dc2, np.co, 1);
-            const LnRed ro{Y(n, R), lo.gamma, lo.stats};
-            const int ps = conv_dgrad(En, h, w, dso, c.dc2, 0, c.dc2, np.co, nk, 1, dln, nk, 0, 0, &ro);
-            ln_bwd(En, Y(n, R), dln, lo, npx * nk, dy, 0, np.ln_out_g, np.ln_out_b, ps);
-            return;
-        }
-        if (k == 1 + 3 * R) {
-            conv_wgrad(En, h, w, u1c, c.dc1, 0, c.dc1, raw, dy, nk, 0, nk, np.ci, 1);
-            conv_dgrad(En, h, w, dy, nk, 0, nk, np.ci, c.dc1, 1, du1c, c.dc1, 0, 0);
-            return;
-        }
-        // the weight gradients run behind the chain on En.wst; before the chain overwrites a dY buffer
-        // it waits for the weight gradients reading it (of the block before: dt2, dt1; this block: dy)
-        const int r = R - 1 - (k - 1) / 3, part = (k - 1) % 3;
-        const RBParams& rb = np.rb[r];
-        if (part == 0) {   // conv_b (y_{r+1} = y_r + conv_b(LN3(t2_r)))
-            const LnIn l3 = lnin(n, 2 * R + 1 + r, rb.ln3g, rb.ln3b);
-            ev_cb[n] = conv_wgrad(En, h, w, T2(n, r), gc, 0, gc, l3, dy, nk, 0, nk, rb.cb, 1);
-            const LnRed r3{T2(n, r), l3.gamma, l3.stats};
-            const int ps = conv_dgrad(En, h, w, dy, nk, 0, nk, rb.cb, gc, 1, dcb, gc, 0, 0, &r3);
-            chain_wait(En, ev_gc[n]);
-            ln_bwd(En, T2(n, r), dcb, l3, npx * gc, dt2, 0, rb.ln3g, rb.ln3b, ps);
-        } else if (part == 1) {   // grouped dilated branches
-            const LnIn l2 = lnin(n, R + 1 + r, rb.ln2g, rb.ln2b);
-            // the LN2 reduction rides on the branches' data gradients when their windows are pairwise disjoint
-            // (the reference group mode's closure windows [(card - 1) w, card w) of each branch width w): each
-            // element of dbuf is then final after the one launch that writes it, and each launch adds its
-            // window's partials after the previous launches'
-            const int nb = (int)c.br.size();
-            bool disjoint = true;
-            unsigned long long wmask = 0;
-            for (int i = 0; i < nb; i++) {
-                for (int j = i + 1; j < nb; j++)
-                    disjoint = disjoint && (c.br[i].cin_off + c.br[i].cin <= c.br[j].cin_off ||
-                                            c.br[j].cin_off + c.br[j].cin <= c.br[i].cin_off);
-                for (int ch = c.br[i].cin_off; ch < c.br[i].cin_off + c.br[i].cin && ch < 64; ch++) wmask |= 1ull << ch;
-            }
-            // disjoint windows over <= 64 channels: the branches store their windows (no accumulate) and the
-            // LN2 backward reads the channels outside them as 0 (channel mask), so dbuf is not zeroed first
-            const bool masked = disjoint && nk <= 64 && ln2_mask();
-            if (!masked) hchk(hipMemsetAsync(dbuf, 0, (size_t)B * npx * nk * 4, En.st), "hipMemsetAsync");
-            int ps = 0;
-            bool fused = disjoint;
-            for (int bi = 0; bi < nb; bi++) {
-                const Branch& b = c.br[bi];
-                ev_gc[n] = conv_wgrad(En, h, w, T1(n, r), nk, b.cin_off, b.cin, l2, dt2, gc, b.out_off, b.cout,
-                                      rb.gc[bi], b.dil);
-                LnRed r2{T1(n, r), l2.gamma, l2.stats};
-                r2.base = ps;
-                const int np = conv_dgrad(En, h, w, dt2, gc, b.out_off, b.cout, rb.gc[bi], b.cin, b.dil, dbuf, nk,
-                                          b.cin_off, masked ? 0 : 1, fused ? &r2 : nullptr);
-                fused = fused && np > 0;
-                ps += np;
-            }
-            if (!fused) ps = 0;   // (k_lnb_reduce, over whatever partials were written)
-            chain_wait(En, ev_ca[n]);
-            ln_bwd(En, T1(n, r), dbuf, l2, npx * nk, dt1, 0, rb.ln2g, rb.ln2b, ps, masked ? wmask : 0ull,
-                   masked ? nk : 0);
-        } else {   // conv_a
-            const LnIn l1 = lnin(n, r, rb.ln1g, rb.ln1b);
-            ev_ca[n] = conv_wgrad(En, h, w, Y(n, r), nk, 0, nk, l1, dt1, nk, 0, nk, rb.ca, 1);
-            const LnRed r1{Y(n, r), l1.gamma, l1.stats};
-            const int ps = conv_dgrad(En, h, w, dt1, nk, 0, nk, rb.ca, nk, 1, dln, nk, 0, 0, &r1);
-            chain_wait(En, ev_cb[n]);
-            ln_bwd(En, Y(n, r), dln, l1, npx * nk, dy, 1, rb.ln1g, rb.ln1b, ps);
-        }
-    };
-    const int nphase = 2 + 3 * R;
-    if (interleave) {
-        for (int k = 0; k < nphase; k++)
-            for (int n = 0; n < 2; n++) phase(n, k);
-    } else {
-        for (int n = 0; n < 2; n++)
-            for (int k = 0; k < nphase; k++) phase(n, k);
+        const float* y = A.y(n, c.R);
+        const LnIn lo = lnin(n, A.ln.ln_out(), np.ln_out_g, np.ln_out_b);
+        const Src dso = whole<const float>(s.dso, c.dc2);
+        conv_wgrad(X[n], g, whole(y, c.nk), lo, dso, np.co, 1);
+        const LnRed ro{y, lo.gamma, lo.stats};
+        const int ps = conv_dgrad(X[n], g, dso, np.co, 1, whole(s.dln, c.nk), 0, &ro);
+        ln_bwd(X[n], y, s.dln, lo, n_nk, fresh(n, s.dy), 0, np.ln_out_g, np.ln_out_b, ps);
     }
-    stream_wait(E1.st, E.st, tevent(E.p));   // net b's chain done
-    for (int n = 0; n < 2; n++)                  // and both nets' weight gradients
-        if (X[n]->wst) stream_wait(X[n]->wst, E.st, tevent(E.p));
-    // du += the two nets' u1 gradients, net A's first (fixed order: bitwise reproducible)
-    launch_scatter_add_u1c(E.at<float>(E.T.du1c[0]), du, B, c.H, c.W, c.D, c.mask, h, w, c.dc1, E.st);
-    launch_scatter_add_u1c(E.at<float>(E.T.du1c[1]), du, B, c.H, c.W, c.D, c.mask, h, w, c.dc1, E.st);
-}
+
+    // conv_b (y_{r+1} = y_r + conv_b(LN3(t2_r))) and the LN3 backward: dy -> dt2
+    void conv_b(int n, int r) {
+        Scratch& s = S[n];
+        const RBParams& rb = c.net[n].rb[r];
+        const float* t2 = A.t2(n, r);
+        const LnIn l3 = lnin(n, A.ln.ln3(r), rb.ln3g, rb.ln3b);
+        const Src dy = whole<const float>(s.dy.p, c.nk);
+        wgrad(n, whole(t2, c.gc), l3, s.dy, dy, rb.cb);
+        const LnRed r3{t2, l3.gamma, l3.stats};
+        const int ps = conv_dgrad(X[n], g, dy, rb.cb, 1, whole(s.dcb, c.gc), 0, &r3);
+        ln_bwd(X[n], t2, s.dcb, l3, n_gc, fresh(n, s.dt2), 0, rb.ln3g, rb.ln3b, ps);
+    }
+
+    // the grouped dilated branches and the LN2 backward: dt2 -> dt1 (through dbuf, see BranchWindows)
+    void branches(int n, int r) {
+        Scratch& s = S[n];
+        TExec& E = X[n];
+        const RBParams& rb = c.net[n].rb[r];
+        const float* t1 = A.t1(n, r);
+        const LnIn l2 = lnin(n, A.ln.ln2(r), rb.ln2g, rb.ln2b);
+        if (!bwin.masked) hchk(hipMemsetAsync(s.dbuf, 0, (size_t)E.B * n_nk * 4, E.st), "hipMemsetAsync");
+        int ps = 0;
+        bool fused = bwin.disjoint;
+        for (size_t bi = 0; bi < c.br.size(); bi++) {
+            const Branch& b = c.br[bi];
+            const Src dt2 = branch_out<const float>(s.dt2.p, c.gc, b);
+            wgrad(n, branch_in(t1, c.nk, b), l2, s.dt2, dt2, rb.gc[bi], b.dil);
+            LnRed r2{t1, l2.gamma, l2.stats};
+            r2.base = ps;
+            const int np = conv_dgrad(E, g, dt2, rb.gc[bi], b.dil, branch_in(s.dbuf, c.nk, b), bwin.masked ? 0 : 1,
+                                      fused ? &r2 : nullptr);
+            fused = fused && np > 0;
+            ps += np;
+        }
+        if (!fused) ps = 0;   // (k_lnb_reduce, over whatever partials were written)
+        ln_bwd(E, t1, s.dbuf, l2, n_nk, fresh(n, s.dt1), 0, rb.ln2g, rb.ln2b, ps, bwin.masked ? bwin.mask : 0ull,
+               bwin.masked ? c.nk : 0);
+    }
+
+    // conv_a and the LN1 backward: dt1 -> dy (added to the residual path's gradient)
+    void conv_a(int n, int r) {
+        Scratch& s = S[n];
+        const RBParams& rb = c.net[n].rb[r];
+        const float* y = A.y(n, r);
+        const LnIn l1 = lnin(n, A.ln.ln1(r), rb.ln1g, rb.ln1b);
+        const Src dt1 = whole<const float>(s.dt1.p, c.nk);
+        wgrad(n, whole(y, c.nk), l1, s.dt1, dt1, rb.ca);
+        const LnRed r1{y, l1.gamma, l1.stats};
+        const int ps = conv_dgrad(X[n], g, dt1, rb.ca, 1, whole(s.dln, c.nk), 0, &r1);
+        ln_bwd(X[n], y, s.dln, l1, n_nk, fresh(n, s.dy), 1, rb.ln1g, rb.ln1b, ps);
+    }
+
+    void conv_in(int n, int = 0) {
+        Scratch& s = S[n];
+        const NetParams& np = c.net[n];
+        const Src dy = whole<const float>(s.dy.p, c.nk);
+        conv_wgrad(X[n], g, whole<const float>(u1c, c.dc1), LnIn{}, dy, np.ci, 1);
+        conv_dgrad(X[n], g, dy, np.ci, 1, whole(s.du1c, c.dc1), 0);
+    }
+
+    void run(const float* u, const float* dv, float* du) {
+        TExec& E = X[0];
+        hipStream_t side = X[1].st;
+        launch_gather_u1c(u, u1c, E.B, c.H, c.W, c.D, c.mask, c.hc, c.wc, c.dc1, E.st);
+        stream_wait(E.st, side, tevent(E.p));   // u1c gathered
+        for (int n = 0; n < 2 && !saved; n++) recompute(n);
+        stream_wait(side, E.st, tevent(E.p));   // both nets' outputs
+        law(u, dv, du);
+        stream_wait(E.st, side, tevent(E.p));   // dL/d s_pre, dL/dt
+        // a net's chain, last conv first
+        using S = StreamedBwd;
+        std::vector<Step> steps{{&S::conv_out, 0}};
+        for (int r = c.R - 1; r >= 0; r--)
+            for (auto stage : {&S::conv_b, &S::branches, &S::conv_a}) steps.push_back({stage, r});
+        steps.push_back({&S::conv_in, 0});
+        // The two chains are enqueued interleaved, step by step: the GPU starts a stream's kernels in about
+        // the order the host submitted them across streams (measured: no kernel ran more than ~15
+        // submissions ahead of the newest finished one), so a chain enqueued whole after the other only
+        // overlapped it at the end. SCHED_NET_OUTER enqueues net A's chain, then net b's.
+        if ((opts().train_sched & SCHED_NET_OUTER) == 0) {
+            for (Step s : steps)
+                for (int n = 0; n < 2; n++) (this->*s.stage)(n, s.r);
+        } else {
+            for (int n = 0; n < 2; n++)
+                for (Step s : steps) (this->*s.stage)(n, s.r);
+        }
+        stream_wait(side, E.st, tevent(E.p));   // net b's chain done
+        for (int n = 0; n < 2; n++)             // and both nets' weight gradients
+            if (X[n].wst) stream_wait(X[n].wst, E.st, tevent(E.p));
+        scatter_du1c(E, c, du, E.st);
+    }
+};
 
 }  // namespace
 
 void flow_backward(Plan& p, const float* params, const float* xy, const float* zy, void* workspace, int B,
                    float inv_batch, float* dparams, hipStream_t st, const float* count, LayerDoneFn done, void* user) {
-    TExec E{p, params, dparams, (char*)workspace, p.layout(B), p.train_layout(B), B, st};
+    const TrainLayout TL = p.train_layout(B);
+    TExec E = begin_backward(p, TL, params, dparams, workspace, B, st);
     E.inv_batch_ = inv_batch;
     E.count = count;
     E.saved = true;
-    // pooled events: each record of this call gets its own (a re-recorded event that a queued wait still
-    // references serialised the two nets' chains on the GPU); the previous call's waits are all enqueued
-    p.tev_next = 0;
     const WsLayout& L = E.L;
     const int* T = p.dev_table;
-    if (p.n_bw > 0) launch_pack(params, p.dev_bw_map, E.at<float>(E.T.bw), (long long)p.n_bw, st);
-    hchk(hipMemsetAsync(dparams, 0, (size_t)p.n_params * 4, st), "hipMemsetAsync");
-    hchk(hipMemsetAsync(E.at<float>(E.T.zeros), 0, 64 * 4, st), "hipMemsetAsync");
     const int nuv = (int)L.n_uv;
     const cnf_flow_desc& d = p.desc;
     float* dzy = E.at<float>(E.T.dzy);
@@ -841,7 +893,7 @@ void flow_backward(Plan& p, const float* params, const float* xy, const float* z
                 if (c.lds_bwd)
                     coupling_backward_lds(E, c, E.at<float>(E.T.save_u[c.index]), cur, nxt, -1);
                 else
-                    coupling_backward(E, c, E.at<float>(E.T.save_u[c.index]), cur, nxt);
+                    StreamedBwd(E, c).run(E.at<float>(E.T.save_u[c.index]), cur, nxt);
                 // every launch writing this layer's parameter gradients is ordered before anything enqueued
                 // on st from here (its side streams joined st): the caller may reduce them now
                 if (done != nullptr) done(user, c.index);
@@ -866,13 +918,11 @@ void flow_backward(Plan& p, const float* params, const float* xy, const float* z
 
 void coupling_layer_backward(Plan& p, int ci, const float* params, const float* u, const float* dv, float* du,
                              float g_ld, void* workspace, int B, float* dparams, hipStream_t st) {
-    TExec E{p, params, dparams, (char*)workspace, p.layout(B), p.train_layout(B), B, st};
+    const TrainLayout T = p.train_layout(B);
+    TExec E = begin_backward(p, T, params, dparams, workspace, B, st);
     E.inv_batch_ = -g_ld;
-    p.tev_next = 0;
-    if (p.n_bw > 0) launch_pack(params, p.dev_bw_map, E.at<float>(E.T.bw), (long long)p.n_bw, st);
-    hchk(hipMemsetAsync(dparams, 0, (size_t)p.n_params * 4, st), "hipMemsetAsync");
-    hchk(hipMemsetAsync(E.at<float>(E.T.zeros), 0, 64 * 4, st), "hipMemsetAsync");
-    coupling_backward(E, p.couplings[ci], u, dv, du);
+    // (a lone layer has no saved activations: E.saved stays false and the layer recomputes them)
+    StreamedBwd(E, p.couplings[ci]).run(u, dv, du);
     hchk(hipGetLastError(), "training kernel launch");
 }
 

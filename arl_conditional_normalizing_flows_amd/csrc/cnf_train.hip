@@ -686,11 +686,9 @@ __global__ __launch_bounds__(256, 2) void k_tconv_thin(TConvArgs a, int TR) {
     if (lnr) lnr_finish(a, sg, sgh, b);
 }
 
-// debug option TRAIN_ALT bit 8: no thin-K convolutions (the MFMA kernels take them)
-static bool tconv_thin_on() { return (opts().train_alt & 8) == 0; }
+static bool tconv_thin_on() { return (opts().train_alt & ALT_NO_THIN) == 0; }
 
-// debug option TRAIN_ALT bit 1: the register-blocked VALU kernels
-static bool train_valu() { return (opts().train_alt & 1) != 0; }
+static bool train_valu() { return (opts().train_alt & ALT_VALU) != 0; }
 bool train_valu_kernels() { return train_valu(); }
 
 int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
@@ -701,7 +699,7 @@ int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
         if (a.lnr_part != nullptr && a.lnr_base + (int)(g.x * g.z) > a.lnr_stride) a.lnr_part = nullptr;
         return a.lnr_part != nullptr ? (int)(g.x * g.z) : 0;
     };
-    const bool band_off = (opts().train_alt & 4) != 0;   // debug option TRAIN_ALT bit 4: no band-staged 3x3 kernel
+    const bool band_off = (opts().train_alt & ALT_NO_TCONV_BAND) != 0;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (!train_valu() && tconv_thin_on() && a.taps == 9 && a.dil == 1 && a.K >= 1 && a.K <= 4 &&
         a.stats == nullptr && (a.N == 64 || a.N == 32 || a.N == 16) && a.W >= 1 && (a.out_cs & 3) == 0 &&
@@ -1440,7 +1438,7 @@ static void wgrad_thin_shape(int B, int H, int W, int& TR, int& ipw, int& ntile)
 }
 
 bool wgrad_thin_ok(int H, int W, int taps, int dil, int CI, int CO) {
-    const bool on = (opts().train_alt & 8) == 0;   // debug option TRAIN_ALT bit 8: k_wgrad_direct / k_wgrad_band take them
+    const bool on = (opts().train_alt & ALT_NO_THIN) == 0;
     if (!on || taps != 9 || dil != 1 || CO < 1 || CO > 4 || CI < 4 || CI > 64 || (CI & 3) != 0 || W < 1 || W > 128)
         return false;
     int TR, ipw, ntile;
