@@ -41,6 +41,11 @@ class cnf_toy_desc(C.Structure):
                 ('lambda_y', C.c_float)]
 
 
+class cnf_sample_desc(C.Structure):
+    _fields_ = [('num_samples', C.c_int), ('chunk', C.c_int), ('temperature', C.c_float),
+                ('seed', C.c_uint64), ('offset', C.c_uint64), ('logit_a', C.c_float), ('residual', C.c_int)]
+
+
 # per-layer completion callback of cnf_flow_backward_ex (void (*)(void* user, int coupling_index))
 LAYER_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
@@ -63,6 +68,8 @@ _SIGS = [
     ('cnf_flow_forward_noise', C.c_int, [_P, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_uint64, _F, _F, _F, _P,
                                          C.c_int, _P]),
     ('cnf_flow_inverse', C.c_int, [_P, _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_plan_sample_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_sample_desc)]),
+    ('cnf_flow_sample', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_forward', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_squeeze', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -111,6 +111,35 @@ __device__ __forceinline__ float logit_value(float v, const LogitK& k) {
     const float e = fmaf(k.c1, v, k.a);
     return (logf(e / (1.f - e)) - k.lo) / k.span;
 }
+// de_logitify (:287-318), the inverse map: (logistic(v span + lo) - a) / (b (1 - a)); k_logit and the
+// sampler's post-transform (k_sample_fold) share this expression
+__device__ __forceinline__ float delogit_value(float v, const LogitK& k) {
+    const float z = v * k.span + k.lo;
+    return (1.f / (1.f + expf(-z)) - k.a) * k.inv_bc;
+}
+// Running statistics of the draws of one sampled element (cnf_flow_sample): the shifted sums the LN
+// partials use (ln_partial above), (K, S1, S2) with K the first draw's value, S1 = sum (v - K),
+// S2 = sum (v - K)^2 over the draws so far in draw order. The shift keeps S2 - S1^2/S from cancelling
+// when the values sit far above their spread (a residual sample x + y with a large y; the value-regime
+// defects of DESIGN.md section 3). The state is three floats whether it lives in registers inside a
+// chunk or in the workspace between chunks, so the result does not depend on where chunks are cut.
+__device__ __forceinline__ void sample_fold(float v, bool first, float& K, float& S1, float& S2) {
+    if (first) {
+        K = v;
+        S1 = 0.f;
+        S2 = 0.f;
+    } else {
+        const float d = v - K;
+        S1 += d;
+        S2 = fmaf(d, d, S2);
+    }
+}
+// mean = K + S1/S and the population std = sqrt(max(0, (S2 - S1^2/S)/S)) of S folded draws
+__device__ __forceinline__ void sample_finish(float K, float S1, float S2, float S, float& mean, float& std) {
+    mean = K + S1 / S;
+    const float q = (S1 * S1) / S;
+    std = sqrtf(fmaxf(0.f, (S2 - q) / S));
+}
 // InputPrepArgs (cnf_kernels.h) of element g of the batch stream, channel ch: cnf_flow_forward_noise's
 // fused gather and its k_prep fallback use this one expression, bit for bit the k_logit + k_noise passes
 __device__ __forceinline__ float input_prep_value(float x, int ch, const InputPrepArgs& q, uint64_t g) {

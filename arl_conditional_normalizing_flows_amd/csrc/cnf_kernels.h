@@ -450,6 +450,38 @@ void launch_nll(const float* xy, const float* zy, const float* ld, float* per_im
                 int B, int HW, int D, int x_d, float lambda_y, hipStream_t st);
 void launch_pack(const float* params, const int64_t* map, float* aux, long long n, hipStream_t st);
 
+// ---- conditional sampling (cnf_sample.hip, cnf_flow_sample) -------------------------------------
+// One chunk of the B*S images of a sampling call: images g0 .. g0 + n - 1 of the flat [B][S] order
+// (condition g / S, draw g % S), whose zy / xy_hat live in the chunk buffers at image g - g0.
+struct SampleChunk {
+    long long g0;        // first image of the chunk in [B][S] order
+    int n, S;            // images in the chunk, draws per condition
+    int HW, D, x_d;      // io shape
+};
+// k_latent: zy[i] = concat(temperature * N(0,1), y[(g0 + i) / S]) for the chunk's images; the normal
+// of image g, pixel p, channel c is stream element offset + (g * HW + p) * x_d + c (instance_noise_value)
+void launch_latent(const SampleChunk& c, const float* y, float* zy, float temperature, unsigned long long seed,
+                   unsigned long long offset, hipStream_t st);
+// k_sample_fold: one pass over the chunk's xy_hat. Per element (b, p, c < x_d) of the conditions the
+// chunk touches, over the chunk's draws of b in draw order: v = x_hat, de_logitify if logit, + y[b] if
+// residual; stored to samples [B][S][HW][x_d] (non-null); folded into state [3][B][HW][x_d] = (K, S1, S2)
+// (sample_fold; loaded unless the chunk holds b's first draw), and with b's last draw mean / std
+// [B][HW][x_d] (each may be null) are written. state == null: no statistics.
+struct SampleFoldArgs {
+    const float* xy_hat;
+    const float* y;
+    float* samples;
+    float* state;
+    float* mean;
+    float* std;
+    int B, logit, residual;
+    LogitK lk;
+};
+void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream_t st);
+// k_sample_ydev: y_dev[g0 + i] = sum_{p, c >= x_d} |xy_hat[i, p, c] - y[(g0 + i) / S, p, c - x_d]|, one
+// wave per image, fp64 lane sums in element order then a fixed-order wave sum
+void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st);
+
 
 // ---- training (cnf_train.hip) -------------------------------------------------------------------
 // Generic fp32 convolution for the training path over the dense backward image (taps x k x n):

@@ -617,8 +617,9 @@ int cnf_adam_step(float* params, const float* grads, float* m, float* v, int64_t
     CNF_CATCH
 }
 
+// append: keep the launches recorded so far (cnf_flow_sample records one inverse per chunk)
 static void flow_inverse(Plan& p, const float* params, const float* aux, const float* zy, float* xy, void* workspace,
-                         int B, hipStream_t stream);
+                         int B, hipStream_t stream, bool append = false);
 
 int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux, const float* zy, float* xy,
                      void* workspace, int B, void* stream) {
@@ -636,9 +637,9 @@ int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux, cons
 
 // cFlow.call(zy, -1) (:1774-1798) as a launch schedule
 static void flow_inverse(Plan& p, const float* params, const float* aux, const float* zy, float* xy, void* workspace,
-                         int B, hipStream_t stream) {
+                         int B, hipStream_t stream, bool append) {
     if (!p.dry) ensure_tables(p);
-    p.recorded.clear();
+    if (!append) p.recorded.clear();
     Exec E{p, params, aux, (char*)workspace, p.layout(B), B, stream};
     const WsLayout& L = E.L;
     float* buf[2] = {E.at<float>(L.uv[0]), E.at<float>(L.uv[1])};
@@ -713,6 +714,111 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
     }
     if (!p.dry) check_launch();
 }
+
+// ---- conditional sampling (include/cnf.h cnf_flow_sample; kernels: cnf_sample.hip) -----------------
+// the sample workspace: the inverse workspace of `chunk` images, one chunk of zy and of xy_hat, and the
+// statistics state (K, S1, S2) [3][B][H][W][x_d]
+struct SampleLayout {
+    size_t zy = 0, xy = 0, state = 0, total = 0;
+};
+static SampleLayout sample_layout(const Plan& p, int B, int chunk) {
+    const cnf_flow_desc& d = p.desc;
+    const size_t n_uv = (size_t)d.io_h * d.io_w * d.io_d;
+    SampleLayout L;
+    size_t off = align_up(p.layout(chunk).total, 256);
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    L.zy = take((size_t)chunk * n_uv * 4);
+    L.xy = take((size_t)chunk * n_uv * 4);
+    L.state = take((size_t)3 * B * d.io_h * d.io_w * d.x_d * 4);
+    L.total = off;
+    return L;
+}
+
+// the argument errors of cnf_flow_sample that need no pointer but the descriptor (null: fine)
+static const char* sample_desc_error(const Plan& p, int B, const cnf_sample_desc* s) {
+    if (s == nullptr) return "null sample descriptor";
+    if (B < 1) return "B must be >= 1";
+    if (s->num_samples < 1) return "num_samples must be >= 1";
+    if (s->chunk < 1) return "chunk must be >= 1";
+    if (!(s->temperature >= 0.f) || std::isinf(s->temperature)) return "temperature must be finite and >= 0";
+    if (s->logit_a != 0.f && !(s->logit_a > 0.f && s->logit_a < 0.5f))
+        return "logit_a must be 0 (no de_logitify) or in (0, 0.5)";
+    if (s->residual != 0 && p.desc.io_d - p.desc.x_d != p.desc.x_d)
+        return "residual needs y of x's depth (io_d - x_d == x_d)";
+    return nullptr;
+}
+
+extern "C" {
+
+size_t cnf_plan_sample_workspace_bytes(const cnf_plan* plan, int B, const cnf_sample_desc* desc) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!plan) return 0;
+    if (const char* e = sample_desc_error(*plan->p, B, desc)) {   // (the message for cnf_last_error)
+        (void)fail(CNF_E_INVALID, std::string("cnf_plan_sample_workspace_bytes: ") + e);
+        return 0;
+    }
+    return sample_layout(*plan->p, B, desc->chunk).total;
+}
+
+int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                    const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                    void* workspace, int B, void* stream) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!plan || !params || !aux || !workspace) return fail(CNF_E_INVALID, "cnf_flow_sample: null argument");
+    if (!y) return fail(CNF_E_INVALID, "cnf_flow_sample: null y");
+    if (const char* e = sample_desc_error(*plan->p, B, desc)) return fail(CNF_E_INVALID, std::string("cnf_flow_sample: ") + e);
+    if (!samples && !mean && !std && !y_dev)
+        return fail(CNF_E_INVALID, "cnf_flow_sample: no output requested (samples, mean, std, y_dev all null)");
+    CNF_TRY
+    Plan& p = *plan->p;
+    const cnf_flow_desc& d = p.desc;
+    ensure_tables(p);
+    p.recorded.clear();
+    const SampleLayout SL = sample_layout(p, B, desc->chunk);
+    char* ws = (char*)workspace;
+    float* zy = reinterpret_cast<float*>(ws + SL.zy);
+    float* xy = reinterpret_cast<float*>(ws + SL.xy);
+    const bool stats = mean != nullptr || std != nullptr;
+    SampleFoldArgs fa;
+    std::memset(&fa, 0, sizeof(fa));
+    fa.xy_hat = xy;
+    fa.y = y;
+    fa.samples = samples;
+    fa.state = stats ? reinterpret_cast<float*>(ws + SL.state) : nullptr;
+    fa.mean = mean;
+    fa.std = std;
+    fa.B = B;
+    fa.logit = desc->logit_a != 0.f ? 1 : 0;
+    fa.residual = desc->residual != 0 ? 1 : 0;
+    if (fa.logit) fa.lk = logit_consts(desc->logit_a);
+    const float T = desc->temperature;
+    const unsigned long long seed = desc->seed, off = desc->offset;
+    const long long total = (long long)B * desc->num_samples;
+    const double px = (double)d.io_h * d.io_w;
+    for (long long g0 = 0; g0 < total; g0 += desc->chunk) {
+        const int n = (int)std::min<long long>(desc->chunk, total - g0);
+        const SampleChunk c{g0, n, desc->num_samples, d.io_h * d.io_w, d.io_d, d.x_d};
+        Exec E{p, params, aux, ws, p.layout(n), n, (hipStream_t)stream};
+        E.record("k_latent", 0, 4.0 * n * px * (2 * d.io_d - d.x_d),
+                 [=](void* st) { launch_latent(c, y, zy, T, seed, off, (hipStream_t)st); });
+        flow_inverse(p, params, aux, zy, xy, ws, n, (hipStream_t)stream, true);
+        if (samples != nullptr || stats)
+            E.record("k_sample_fold", 0, 4.0 * n * px * d.x_d * (samples ? 2 : 1),
+                     [=](void* st) { launch_sample_fold(c, fa, (hipStream_t)st); });
+        if (y_dev != nullptr)
+            E.record("k_sample_ydev", 0, 8.0 * n * px * (d.io_d - d.x_d),
+                     [=](void* st) { launch_sample_ydev(c, xy, y, y_dev, (hipStream_t)st); });
+    }
+    check_launch();
+    return CNF_OK;
+    CNF_CATCH
+}
+
+}  // extern "C"
 
 static void dry_run(Plan& p, int B, int direction) {
     p.dry = true;

@@ -36,14 +36,7 @@ __global__ __launch_bounds__(256) void k_logit(const float* __restrict__ x, floa
                                                LogitK k, int inverse) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float v = x[i];
-        float r;
-        if (!inverse) {
-            r = logit_value(v, k);
-        } else {   // de_logitify (:306-318): (logistic(v span + lo) - a) / (b (1 - a))
-            const float z = v * k.span + k.lo;
-            r = (1.f / (1.f + expf(-z)) - k.a) * k.inv_bc;
-        }
-        out[i] = r;
+        out[i] = !inverse ? logit_value(v, k) : delogit_value(v, k);   // de_logitify (:306-318)
     }
 }
 

@@ -534,6 +534,57 @@ class cFlow:
             vu, zy = layer.backward(vu, zy)
         return vu
 
+    # -- sampling -------------------------------------------------------------------------------
+    def sample(self, y, num_samples, temperature=1.0, seed=0, offset=0, chunk=None, logit_a=None, residual=False,
+               return_samples=True, return_stats=True, return_y_dev=False):
+        """num_samples draws of x given each condition y and their per-pixel statistics: the recipe of
+        TOYcINN.py:807-817 (z from the prior, concat y, the model in the generative direction, :1774-1798)
+        with the post-transforms and the reduction over the draws, in one native call (cnf_flow_sample).
+
+        y: [B,H,W,D-x_d] on the device, or [H,W,D-x_d] for one condition. The latent of condition b, draw s
+        is temperature * renew_noise of a [B,S,H,W,x_d] tensor at (seed, offset); every drawn x goes through
+        de_logitify(., logit_a) when logit_a is given, then + y when residual (RESIDUAL=True super-resolution:
+        needs D - x_d == x_d). The B*S images run through the inverse `chunk` at a time (default
+        min(B*S, 64)); no result depends on chunk, bit for bit.
+
+        Returns a dict with the requested ones of 'samples' [B,S,H,W,x_d], 'mean' and 'std' [B,H,W,x_d]
+        (over the draws, population form: np.std) and 'y_dev' [B,S] (sum |y_hat - y| of each draw: how
+        well it honours its condition). With return_samples=False no [B,S,...] tensor is allocated."""
+        y = _as_input(y, 'y')
+        H, W, D = self.io_shape
+        if y.dim() == 3:
+            y = y.unsqueeze(0)
+        if tuple(y.shape[1:]) != (H, W, D - self.x_d):
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {H}, {W}, {D - self.x_d}]')
+        B, S = int(y.shape[0]), int(num_samples)
+        if chunk is None:
+            chunk = max(1, min(B * S, 64))
+        desc = _lib.cnf_sample_desc(S, int(chunk), float(temperature), int(seed) & (2 ** 64 - 1),
+                                    int(offset) & (2 ** 64 - 1), float(logit_a or 0.0), int(bool(residual)))
+        lib = _lib.load()
+        key = ('sample', B, S, int(chunk))
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(lib.cnf_plan_sample_workspace_bytes(self._plan, B, C.byref(desc)))
+            if nbytes <= 0:   # an argument error, as the reference's asserts
+                raise AssertionError(f'cFlow.sample: {lib.cnf_last_error().decode()}')
+            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+
+        def new(*shape):
+            return torch.empty(shape, device=y.device, dtype=torch.float32)
+        out = {}
+        if return_samples:
+            out['samples'] = new(B, max(S, 0), H, W, self.x_d)
+        if return_stats:
+            out['mean'], out['std'] = new(B, H, W, self.x_d), new(B, H, W, self.x_d)
+        if return_y_dev:
+            out['y_dev'] = new(B, max(S, 0))
+        check(lib.cnf_flow_sample(self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc),
+                                  ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')),
+                                  ptr(out.get('y_dev')), ptr(ws), B, _stream()),
+              'cnf_flow_sample')
+        return out
+
     # -- loss -----------------------------------------------------------------------------------
     def nll_sums(self, xy, zy=None, logdet_per_image=None):
         """Per-batch sums of the NLL terms on device: (sum loss_i, sum -llz_i, sum -lly_i,

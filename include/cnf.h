@@ -164,6 +164,49 @@ int cnf_flow_forward_noise(cnf_plan* plan, const float* params, const float* aux
 int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux,
                      const float* zy, float* xy, void* workspace, int B, void* stream);
 
+/* Conditional sampling: S draws of x given y for each of B conditions, and their per-pixel
+ * statistics. Replaces the recipe the reference's users write by hand (TOYcINN.py:807-817: draw z
+ * from the prior, concatenate the condition y, call the model in the generative direction,
+ * conv_cINN_make_model.py:1774-1798) together with the post-transforms and the reduction over
+ * the draws that follow it.
+ *
+ * Latent: with H, W, D = io shape, the latent of condition b, draw s, pixel p, channel c < x_d is
+ * temperature * element offset + ((b*S + s)*H*W + p)*x_d + c of the seed's stream, i.e. exactly
+ * what cnf_instance_noise(NULL, out, B*S*H*W*x_d, 0, seed, offset) writes into a [B,S,H,W,x_d]
+ * tensor, times temperature in one fp32 multiply; zy[b,s] = concat(latent, y[b]) in the xy layout.
+ * Inverse and post-transforms: xy_hat = cnf_flow_inverse(zy); per drawn value take x_hat (the
+ * first x_d channels), apply de_logitify (cnf_logit(., a, inverse)) if logit_a, then add the INPUT
+ * y (not y_hat) if residual. `samples` holds these values; `mean` and `std` are over the S draws of
+ * each condition in population form (divide by S, as np.std and tf.math.reduce_std do);
+ * y_dev[b,s] = sum_{h,w,c} |y_hat - y| of that draw, the unweighted sum of log_loss's lly term
+ * (:1815-1848): whether the draw honours its condition.
+ * The B*S images run through the inverse `chunk` at a time; no result depends on chunk, bit for
+ * bit (the per-element statistics are carried across chunks in draw order as a shifted sum
+ * (K, S1, S2), K the first draw's value, S1 = sum (v - K), S2 = sum (v - K)^2, and
+ * mean = K + S1/S, std = sqrt(max(0, (S2 - S1^2/S)/S))). */
+typedef struct cnf_sample_desc {
+    int   num_samples;   /* S >= 1 draws per condition */
+    int   chunk;         /* images per inverse call, >= 1; results do not depend on it */
+    float temperature;   /* z = temperature * N(0,1); >= 0 (0: the mode of the prior) */
+    uint64_t seed, offset; /* Philox stream, as cnf_instance_noise */
+    float logit_a;       /* 0: none; in (0,0.5): de_logitify(., a) on every drawn x value */
+    int   residual;      /* 1: x + y per sample (preprocess_dataset_SR RESIDUAL=True);
+                            needs io_d - x_d == x_d */
+} cnf_sample_desc;
+
+/* Workspace bytes of cnf_flow_sample for B conditions: cnf_plan_workspace_bytes(desc->chunk), the
+ * zy and xy_hat buffers of one chunk and the statistics state (3*B*H*W*x_d floats); independent of
+ * num_samples. 0 for a NULL or invalid argument. */
+size_t cnf_plan_sample_workspace_bytes(const cnf_plan* plan, int B, const cnf_sample_desc* desc);
+
+/* y: [B][H][W][D - x_d]. Outputs, each may be NULL but not all: samples [B][S][H][W][x_d], mean and
+ * std [B][H][W][x_d], y_dev [B][S]. CNF_E_INVALID before any HIP call for: NULL y, S < 1, chunk < 1,
+ * temperature < 0 or not finite, logit_a outside {0} u (0, 0.5), residual with D - x_d != x_d, no
+ * output requested, B < 1. The launches are recorded as cnf_flow_inverse's (measurement hooks). */
+int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                    const cnf_sample_desc* desc, float* samples, float* mean, float* std,
+                    float* y_dev, void* workspace, int B, void* stream);
+
 /* coupling_layer.forward_and_Jacobian (:1258-1328) for layer `layer` of
  * layers_list: u -> v (shape of the layer's in_shape); logdet_accum[B] +=
  * per-image sum of A(u1) (pass NULL to skip). u and v must not alias. */
