@@ -86,6 +86,9 @@ _SIGS = [
     ('cnf_toy_num_params', C.c_int64, [C.POINTER(cnf_toy_desc)]),
     ('cnf_toy_call', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _F, _F, C.c_int, C.c_int, _P]),
     ('cnf_toy_nll_sums', C.c_int, [_F, _F, C.c_int, _P]),
+    ('cnf_toy_train_workspace_bytes', C.c_size_t, [C.POINTER(cnf_toy_desc), C.c_int]),
+    ('cnf_toy_forward_train', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_toy_backward', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _P, C.c_int, C.c_float, _F, _P]),
     ('cnf_logit', C.c_int, [_F, _F, C.c_int64, C.c_float, C.c_int, _P]),
     ('cnf_sr_preprocess', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_down', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -357,8 +357,30 @@ struct ToyArgs {
     float lambda_y;
     int order[TOY_MAXL];        // mask_indices
     int net_off[TOY_MAXL + 1];  // float offset of network j's parameters
+    float* save_u;              // [nl][B][3] input of every executed coupling layer, by step (training) or null
 };
 void launch_toy(const ToyArgs& a, int lds_floats, hipStream_t st);
+// k_toy_bwd / k_toy_grad_sum (cnf_toy_train.hip): backward of the whole toy flow, one workgroup per
+// TOY_TS consecutive samples, one partial gradient row per workgroup, then the tile-order sum
+#ifndef CNF_TOY_TS
+#define CNF_TOY_TS 16   // a multiple of 16; -DCNF_TOY_TS=32 / 64 builds the variants DESIGN.md compares
+#endif
+constexpr int TOY_TS = CNF_TOY_TS;
+struct ToyBwdArgs {
+    const float* params;
+    const float* xy;       // [B][3]
+    const float* zy;       // [B][3]
+    const float* saved_u;  // [nl][B][3], as ToyArgs::save_u wrote it
+    float* part;           // [tiles][num_params]
+    int B, nl, H, L, x_d, HP, num_params;
+    float lambda_y, inv_batch;
+    int order[TOY_MAXL];
+    int net_off[TOY_MAXL + 1];
+};
+int toy_bwd_hp(int H);                   // LDS row stride of one sample's hidden vector
+size_t toy_bwd_lds_bytes(int H, int L);  // dynamic LDS of k_toy_bwd
+void launch_toy_bwd(const ToyBwdArgs& a, hipStream_t st);
+void launch_toy_grad_sum(const float* part, int tiles, int num_params, float* dparams, hipStream_t st);
 void launch_nll_sums(const float* per_image, float* sums, int B, hipStream_t st);
 void launch_net_lds(const NetLdsArgs& a, int B, int lds, hipStream_t st);
 int netlds_num_shapes();   // shape-specialised k_net_lds instantiations compiled in

@@ -989,15 +989,9 @@ int64_t cnf_toy_num_params(const cnf_toy_desc* d) {
     CNF_CATCH
 }
 
-int cnf_toy_call(const cnf_toy_desc* d, const float* params, const float* u, float* v, float* log_detJ,
-                 float* per_sample, int B, int direction, void* stream) {
-    CNF_TRY
-    toy_check(d);
-    if (!params || !u || !v || B < 0) return fail(CNF_E_INVALID, "null pointer or negative batch");
-    if (direction != 1 && direction != -1) return fail(CNF_E_INVALID, "direction must be +1 or -1");
-    if (u == v) return fail(CNF_E_INVALID, "u and v must not alias");
-    if (B == 0) return CNF_OK;
-    ToyArgs a;
+// k_toy's launch arguments for direction `direction`; returns the LDS staging floats (the largest coupling network)
+static int64_t toy_args(const cnf_toy_desc* d, const float* params, const float* u, float* v, float* log_detJ,
+                        float* per_sample, int B, int direction, ToyArgs& a) {
     std::memset(&a, 0, sizeof(a));
     a.params = params;
     a.u = u;
@@ -1021,9 +1015,96 @@ int cnf_toy_call(const cnf_toy_desc* d, const float* params, const float* u, flo
         maxn = std::max(maxn, n);
     }
     a.net_off[a.nl] = (int)off;
+    return maxn;
+}
+
+int cnf_toy_call(const cnf_toy_desc* d, const float* params, const float* u, float* v, float* log_detJ,
+                 float* per_sample, int B, int direction, void* stream) {
+    CNF_TRY
+    toy_check(d);
+    if (!params || !u || !v || B < 0) return fail(CNF_E_INVALID, "null pointer or negative batch");
+    if (direction != 1 && direction != -1) return fail(CNF_E_INVALID, "direction must be +1 or -1");
+    if (u == v) return fail(CNF_E_INVALID, "u and v must not alias");
+    if (B == 0) return CNF_OK;
+    ToyArgs a;
+    const int64_t maxn = toy_args(d, params, u, v, log_detJ, per_sample, B, direction, a);
     if (maxn * 4 > 160 * 1024) return fail(CNF_E_INVALID, "toy coupling networks exceed the 160 KiB LDS staging budget");
     launch_toy(a, (int)maxn, (hipStream_t)stream);
     hip_check(hipGetLastError(), "k_toy");
+    return CNF_OK;
+    CNF_CATCH
+}
+
+// ---- TOYcINN training (TOYcINN_make_model.py:453-481) ------------------------------------------
+// training workspace: the saved coupling-layer inputs [nl][B][3], then one partial gradient row per
+// tile of TOY_TS samples [tiles][num_params]
+static size_t toy_saved_bytes(const cnf_toy_desc* d, int B) {
+    return ((size_t)d->num_coupling_layers * B * 3 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+size_t cnf_toy_train_workspace_bytes(const cnf_toy_desc* d, int B) {
+    try {
+        toy_check(d);
+        if (B < 1) throw std::invalid_argument("B must be >= 1");
+        const int64_t n = cnf_toy_num_params(d);
+        const size_t tiles = ((size_t)B + TOY_TS - 1) / TOY_TS;
+        return toy_saved_bytes(d, B) + tiles * (size_t)n * sizeof(float);
+    } catch (const std::exception& e) {
+        fail(CNF_E_INVALID, e.what());
+        return 0;
+    }
+}
+
+int cnf_toy_forward_train(const cnf_toy_desc* d, const float* params, const float* xy, float* zy, float* per_sample,
+                          void* train_workspace, int B, void* stream) {
+    CNF_TRY
+    toy_check(d);
+    if (!params || !xy || !zy || !train_workspace) return fail(CNF_E_INVALID, "null pointer");
+    if (B < 1) return fail(CNF_E_INVALID, "B must be >= 1");
+    if (xy == zy) return fail(CNF_E_INVALID, "xy and zy must not alias");
+    ToyArgs a;
+    const int64_t maxn = toy_args(d, params, xy, zy, nullptr, per_sample, B, -1, a);
+    if (maxn * 4 > 160 * 1024) return fail(CNF_E_INVALID, "toy coupling networks exceed the 160 KiB LDS staging budget");
+    a.save_u = static_cast<float*>(train_workspace);
+    launch_toy(a, (int)maxn, (hipStream_t)stream);
+    hip_check(hipGetLastError(), "k_toy");
+    return CNF_OK;
+    CNF_CATCH
+}
+
+int cnf_toy_backward(const cnf_toy_desc* d, const float* params, const float* xy, const float* zy, void* train_workspace,
+                     int B, float inv_batch, float* dparams, void* stream) {
+    CNF_TRY
+    toy_check(d);
+    if (!params || !xy || !zy || !train_workspace || !dparams) return fail(CNF_E_INVALID, "null pointer");
+    if (B < 1) return fail(CNF_E_INVALID, "B must be >= 1");
+    if (!std::isfinite(inv_batch)) return fail(CNF_E_INVALID, "inv_batch must be finite");
+    if (toy_bwd_lds_bytes(d->intermediate_dims, d->num_layers) > 160 * 1024)
+        return fail(CNF_E_INVALID, "the toy backward's activations exceed the 160 KiB LDS budget");
+    ToyArgs f;
+    toy_args(d, params, xy, nullptr, nullptr, nullptr, B, -1, f);
+    ToyBwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.params = params;
+    a.xy = xy;
+    a.zy = zy;
+    a.saved_u = static_cast<const float*>(train_workspace);
+    a.part = reinterpret_cast<float*>(static_cast<char*>(train_workspace) + toy_saved_bytes(d, B));
+    a.B = B;
+    a.nl = f.nl;
+    a.H = f.H;
+    a.L = f.L;
+    a.x_d = f.x_d;
+    a.HP = toy_bwd_hp(f.H);
+    a.num_params = f.net_off[f.nl];
+    a.lambda_y = d->lambda_y;
+    a.inv_batch = inv_batch;
+    std::memcpy(a.order, f.order, sizeof(a.order));
+    std::memcpy(a.net_off, f.net_off, sizeof(a.net_off));
+    launch_toy_bwd(a, (hipStream_t)stream);
+    hip_check(hipGetLastError(), "k_toy_bwd");
+    launch_toy_grad_sum(a.part, (B + TOY_TS - 1) / TOY_TS, a.num_params, dparams, (hipStream_t)stream);
+    hip_check(hipGetLastError(), "k_toy_grad_sum");
     return CNF_OK;
     CNF_CATCH
 }

@@ -5,7 +5,9 @@
 // the current coupling layer (b: Dense(H)+LReLU, L x [Dense(H)+LReLU], Dense(u2); A: the same then
 // tanh) are staged into LDS once per workgroup and read as broadcasts. fp32 throughout, exact
 // LeakyReLU / tanh / exp as in the reference graph. The workload is tiny (3-dimensional points), so
-// the kernel favours a simple, exact formulation over throughput.
+// the kernel favours a simple, exact formulation over throughput. With ToyArgs::save_u set (the
+// training forward) it also stores every executed coupling layer's input for k_toy_bwd
+// (cnf_toy_train.hip); the arithmetic is the same either way.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -96,6 +98,8 @@ __global__ __launch_bounds__(256) void k_toy(ToyArgs a) {
         __syncthreads();
         for (int e = threadIdx.x; e < n; e += 256) lw[e] = a.params[a.net_off[j] + e];
         __syncthreads();
+        if (a.save_u && valid)   // training forward: the activations the loss sees (k_toy_bwd reads them)
+            for (int c = 0; c < 3; c++) a.save_u[((size_t)step * a.B + s) * 3 + c] = u[c];
         float u1[2] = {u[i1[0]], n1 > 1 ? u[i1[1]] : 0.f};
         float bv[2], av[2];
         const float* p = toy_net<H>(lw, u1, n1, a.H, a.L, n2, bv);

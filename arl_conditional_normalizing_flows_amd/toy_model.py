@@ -1,8 +1,8 @@
 """Drop-in replacement for the reference's `TOYcINN_make_model.cINN_affine` (BASELINE configs[0]).
 
-Same constructor arguments, `call(u, direction=-1)` / `log_loss` / `test_step` / `metrics`
-semantics as TOYcINN_make_model.py:105-506, on torch tensors [B, 3] fp32 on the ROCm device; the
-flow runs in libcnf_hip.so (k_toy) through the C ABI. Note the toy's direction convention is the
+Same constructor arguments, `call(u, direction=-1)` / `log_loss` / `compile` / `train_step` /
+`test_step` / `metrics` semantics as TOYcINN_make_model.py:105-506, on torch tensors [B, 3] fp32 on the ROCm device; the
+flow runs in libcnf_hip.so (k_toy, and k_toy_bwd for the gradient) through the C ABI. Note the toy's direction convention is the
 reverse of cFlow's: -1 maps xy' -> zy (training direction, returns the per-sample log-det),
 +1 maps zy -> xy'.
 
@@ -61,6 +61,7 @@ class cINN_affine:
         self.num_params = int(n)
         self.params = torch.empty(self.num_params, device=self.device, dtype=torch.float32)
         self._init_weights(seed)
+        self._ws = {}   # B -> (training workspace, gradient buffer)
         self.loss_tracker = Mean('loss')
         self.z_loss_tracker = Mean('z_loss')
         self.y_loss_tracker = Mean('y_loss')
@@ -149,13 +150,80 @@ class cINN_affine:
         grp = None if process_group is True else process_group
         return reduce_nll_sums(sums, xy.shape[0], group=grp, all_reduce=process_group is not None)
 
-    def train_step(self, xy):
-        raise NotImplementedError('the NLL training step (backward kernels + Adam) is the next milestone; '
-                                  'see DESIGN.md')
+    # -- training -------------------------------------------------------------------------------
+    def compile(self, optimizer=None):
+        """keras Model.compile(optimizer=Adam(1e-4)) (TOYcINN.py:213-304)."""
+        from .optimizers import Adam
+        self.optimizer = optimizer if optimizer is not None else Adam()
 
-    def test_step(self, xy):
-        """(:483-506) loss without a weight update; updates the Mean trackers."""
-        vals = [t.item() for t in self.log_loss(xy)]
+    def _train_workspace(self, B):
+        """(training workspace, flat gradient buffer), cached per B."""
+        cache = self._ws
+        ws = cache.get(B)
+        if ws is None:
+            nbytes = int(_lib.load().cnf_toy_train_workspace_bytes(C.byref(self._desc), B))
+            if nbytes <= 0:
+                raise RuntimeError(_lib.load().cnf_last_error().decode())
+            ws = (torch.empty(nbytes, device=self.device, dtype=torch.uint8),
+                  torch.empty(self.num_params, device=self.device, dtype=torch.float32))
+            cache[B] = ws
+        return ws
+
+    def gradients(self, xy, process_group=None):
+        """tape.gradient(loss, trainable_variables) of train_step (:453-481) as one flat vector in
+        the canonical parameter order, plus the 4 loss terms (batch means, device scalars). With
+        process_group (True = the default group) the 4 loss sums and the sample count are all-reduced
+        (one 5-float collective) between forward and backward, the backward scales by 1 / the global
+        count, and the gradient is all-reduced after it: both are those of the global batch. (The C
+        ABI takes inv_batch by value, so the data-parallel path reads the reduced count on the host,
+        once per step; without a process group the step has no host read.)"""
+        from .distributed import allreduce_grads, pack_nll_sums
+        xy = _as_input(xy, 'xy')
+        if xy.dim() != 2 or xy.shape[1] != self.io_shape:
+            raise AssertionError(f'xy must have shape (batch, {self.io_shape})')
+        lib = _lib.load()
+        B = xy.shape[0]
+        ws, grads = self._train_workspace(B)
+        zy = torch.empty_like(xy)
+        per = torch.empty((B, 3), device=xy.device, dtype=torch.float32)
+        check(lib.cnf_toy_forward_train(C.byref(self._desc), ptr(self.params), ptr(xy), ptr(zy), ptr(per), ptr(ws),
+                                        B, _stream()), 'cnf_toy_forward_train')
+        sums = torch.empty(4, device=xy.device, dtype=torch.float32)
+        check(lib.cnf_toy_nll_sums(ptr(per), ptr(sums), B, _stream()), 'cnf_toy_nll_sums')
+        buf = pack_nll_sums(sums, B)
+        grp = None if process_group is True else process_group
+        dist = None
+        if process_group is not None:
+            import torch.distributed as tdist
+            if tdist.is_available() and tdist.is_initialized():
+                dist = tdist
+        n_global = B
+        if dist is not None:
+            dist.all_reduce(buf, group=grp)
+            n_global = int(round(float(buf[4])))   # the C ABI takes inv_batch by value
+        check(lib.cnf_toy_backward(C.byref(self._desc), ptr(self.params), ptr(xy), ptr(zy), ptr(ws), B,
+                                   1.0 / n_global, ptr(grads), _stream()), 'cnf_toy_backward')
+        if dist is not None:
+            allreduce_grads(grads, group=grp)
+        m = buf[:4] / buf[4]
+        return grads, (m[0], m[1], m[2], m[3])
+
+    def train_step(self, xy, process_group=None):
+        """cINN_affine.train_step (:453-481): NLL gradient (GradientTape), optimizer.apply_gradients,
+        Mean trackers; returns {'loss', 'z_loss', 'y_loss', 'detJ_loss'} as 0-d device tensors (no host
+        read in the step). Data-parallel with process_group: see gradients."""
+        if getattr(self, 'optimizer', None) is None:
+            self.compile()
+        grads, terms = self.gradients(xy, process_group)
+        self.optimizer.apply_flat(self.params, grads)
+        for t, v in zip(self.metrics, terms):   # device scalars: the trackers stay on the device
+            t.update_state(v)
+        return {t.name: t.result() for t in self.metrics}
+
+    def test_step(self, xy, process_group=None):
+        """(:483-506) loss without a weight update; updates the Mean trackers. With process_group
+        the loss terms are global-batch means (log_loss)."""
+        vals = [t.item() for t in self.log_loss(xy, process_group=process_group)]
         for tr, v in zip(self.metrics, vals):
             tr.update_state(v)
         return {tr.name: tr.result() for tr in self.metrics}

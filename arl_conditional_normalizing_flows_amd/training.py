@@ -4,7 +4,7 @@ the annealed instance-noise schedule, over the HIP train_step / test_step.
   fit(...)                       keras Model.fit as conv_cINN.py:617-631 calls it (epochs,
                                  initial_epoch, validation_data, callbacks)
   EarlyStopping                  tf.keras.callbacks.EarlyStopping(monitor='val_loss', patience)
-                                 (conv_cINN.py:140-141)
+                                 (conv_cINN.py:140-141), restore_best_weights (TOYcINN.py)
   CSVLogger                      tf.keras.callbacks.CSVLogger(path, separator=',', append=True)
                                  (:533-536): header 'epoch' + sorted metric names
   ModelCheckpoint                save_weights_only every save_freq batches, '{epoch:02d}' in the
@@ -83,25 +83,41 @@ class Callback:
 
 class EarlyStopping(Callback):
     """monitor='val_loss', mode min, min_delta 0: stop once `patience` epochs pass without an
-    improvement (keras semantics: wait resets on improvement; checked from the second epoch)."""
+    improvement (keras semantics: wait resets on improvement; checked from the second epoch).
+    restore_best_weights=True (keras 2.7; the toy driver's callback, TOYcINN.py:213-304): a device copy
+    of the flat parameter vector is kept at each new best epoch (and after the first epoch, should
+    none ever improve) and put back through model.set_weights -- which repacks cFlow's kernel-side
+    weights (cnf_pack_params) -- when this callback stops the training; a fit that runs out of
+    epochs keeps its last weights."""
 
-    def __init__(self, monitor='val_loss', patience=0, min_delta=0.0):
+    def __init__(self, monitor='val_loss', patience=0, min_delta=0.0, restore_best_weights=False):
         self.monitor, self.patience, self.min_delta = monitor, int(patience), abs(float(min_delta))
-        self.best, self.wait, self.stopped_epoch = math.inf, 0, None
+        self.restore_best_weights = bool(restore_best_weights)
+        self.best, self.wait, self.stopped_epoch, self.best_weights = math.inf, 0, None, None
 
     def on_train_begin(self, logs=None):
-        self.best, self.wait, self.stopped_epoch = math.inf, 0, None
+        self.best, self.wait, self.stopped_epoch, self.best_weights = math.inf, 0, None, None
+
+    def _snapshot(self):
+        p = getattr(self.model, 'params', None)
+        return p.detach().clone() if hasattr(p, 'detach') else self.model.get_weights()
 
     def on_epoch_end(self, epoch, logs=None):
         cur = (logs or {}).get(self.monitor)
         if cur is None:
             return
+        if self.restore_best_weights and self.best_weights is None:
+            self.best_weights = self._snapshot()
         self.wait += 1
         if cur < self.best - self.min_delta:
             self.best, self.wait = cur, 0
+            if self.restore_best_weights:
+                self.best_weights = self._snapshot()
         if self.wait >= self.patience and epoch > 0:
             self.stopped_epoch = epoch
             self.model.stop_training = True
+            if self.restore_best_weights and self.best_weights is not None:
+                self.model.set_weights(self.best_weights)
 
 
 class CSVLogger(Callback):

@@ -324,6 +324,30 @@ int cnf_toy_call(const cnf_toy_desc* d, const float* params, const float* u, flo
  * sum -log_detJ_i); divide by B for the reference's 4-tuple. */
 int cnf_toy_nll_sums(const float* per_sample, float* sums, int B, void* stream);
 
+/* ---- TOYcINN training (cINN_affine.train_step, TOYcINN_make_model.py:453-481: GradientTape
+ * over log_loss :404-451, then the optimizer). Replaces the TF autodiff of the dense flow. ---- */
+
+/* Training workspace bytes for B samples: the saved coupling-layer inputs [layers][B][3] and one
+ * partial gradient row [num_params] per tile of 16 consecutive samples. 0 for an invalid
+ * argument (cnf_last_error says which). */
+size_t cnf_toy_train_workspace_bytes(const cnf_toy_desc* d, int B);
+
+/* cnf_toy_call(..., direction -1) that also saves the input of every coupling layer it executes
+ * into train_workspace (for cnf_toy_backward on the same xy / zy): zy and per_sample[B*3]
+ * (optional, as cnf_toy_call) are bit-identical to cnf_toy_call's. */
+int cnf_toy_forward_train(const cnf_toy_desc* d, const float* params, const float* xy, float* zy,
+                          float* per_sample /* [B*3], as cnf_toy_call */, void* train_workspace,
+                          int B, void* stream);
+
+/* dparams[num_params] = d loss / d params for this shard (fully overwritten), where
+ * loss = -(sum_i (llz_i + lly_i + log_detJ_i)) * inv_batch of log_loss (:404-451) and
+ * inv_batch = 1 / global batch size, as in cnf_flow_backward: the dparams of data-parallel shards
+ * add up to the gradient of the batch-mean loss. d|y - y'| / dy = sign(y - y') (0 at 0). The
+ * gradient is taken at the saved activations of cnf_toy_forward_train, not at a re-inverted flow;
+ * it is bitwise reproducible run to run, and a sample's contribution does not depend on B. */
+int cnf_toy_backward(const cnf_toy_desc* d, const float* params, const float* xy, const float* zy,
+                     void* train_workspace, int B, float inv_batch, float* dparams, void* stream);
+
 /* ---- input transforms (the step before the path; conv_cINN_base_functions.py) ----------- */
 
 /* Logit preprocessing of preprocess_dataset_class(LOGITS=True) (:174-231), elementwise over n
