@@ -46,6 +46,11 @@ class cnf_sample_desc(C.Structure):
                 ('seed', C.c_uint64), ('offset', C.c_uint64), ('logit_a', C.c_float), ('residual', C.c_int)]
 
 
+class cnf_toy_sample_desc(C.Structure):
+    _fields_ = [('num_samples', C.c_int), ('temperature', C.c_float), ('seed', C.c_uint64), ('offset', C.c_uint64),
+                ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
+
+
 # per-layer completion callback of cnf_flow_backward_ex (void (*)(void* user, int coupling_index))
 LAYER_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
@@ -89,6 +94,9 @@ _SIGS = [
     ('cnf_toy_train_workspace_bytes', C.c_size_t, [C.POINTER(cnf_toy_desc), C.c_int]),
     ('cnf_toy_forward_train', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_toy_backward', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _P, C.c_int, C.c_float, _F, _P]),
+    ('cnf_toy_sample_workspace_bytes', C.c_size_t, [C.POINTER(cnf_toy_desc), C.c_int, C.POINTER(cnf_toy_sample_desc)]),
+    ('cnf_toy_sample', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, C.POINTER(cnf_toy_sample_desc), _F, _F, _F, _F, _F, _P,
+                                 C.c_int, _P]),
     ('cnf_logit', C.c_int, [_F, _F, C.c_int64, C.c_float, C.c_int, _P]),
     ('cnf_sr_preprocess', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_down', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

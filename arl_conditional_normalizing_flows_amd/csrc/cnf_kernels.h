@@ -381,6 +381,31 @@ int toy_bwd_hp(int H);                   // LDS row stride of one sample's hidde
 size_t toy_bwd_lds_bytes(int H, int L);  // dynamic LDS of k_toy_bwd
 void launch_toy_bwd(const ToyBwdArgs& a, hipStream_t st);
 void launch_toy_grad_sum(const float* part, int tiles, int num_params, float* dparams, hipStream_t st);
+// k_toy_sample / k_toy_sample_stats (cnf_toy_sample.hip, cnf_toy_sample): one workgroup takes one tile of
+// TOY_SAMPLE_TS consecutive draws of one condition from latent to result (tile = s / TOY_SAMPLE_TS; a
+// condition's last tile is zero-padded) and leaves one shifted partial per component; the second kernel merges
+// the partials in tile order
+constexpr int TOY_SAMPLE_TS = 128;   // a multiple of 16
+constexpr int TOY_SAMPLE_PART = 4;   // floats per partial: (n, K, S1, S2)
+struct ToySampleArgs {
+    const float* params;
+    const float* y;        // [B][3 - x_d]
+    float* samples;        // [B][S][x_d] or null
+    float* y_dev;          // [B][S] or null
+    unsigned* hist;        // [B][G] / [B][G][G] or null
+    float* part;           // [B][tiles][x_d][TOY_SAMPLE_PART]
+    int B, S, tiles, nl, H, L, x_d, HP;
+    float temperature;
+    unsigned long long seed, offset;
+    int G;                 // histogram bins per component
+    float lo[2], scale[2];
+    int order[TOY_MAXL];
+    int net_off[TOY_MAXL + 1];
+};
+size_t toy_sample_lds_bytes(int H);   // dynamic LDS of k_toy_sample
+void launch_toy_sample(const ToySampleArgs& a, hipStream_t st);
+void launch_toy_sample_stats(const float* part, int B, int tiles, int S, int x_d, float* mean, float* std,
+                             hipStream_t st);
 void launch_nll_sums(const float* per_image, float* sums, int B, hipStream_t st);
 void launch_net_lds(const NetLdsArgs& a, int B, int lds, hipStream_t st);
 int netlds_num_shapes();   // shape-specialised k_net_lds instantiations compiled in

@@ -1109,6 +1109,101 @@ int cnf_toy_backward(const cnf_toy_desc* d, const float* params, const float* xy
     CNF_CATCH
 }
 
+// ---- TOYcINN sampling (TOYcINN.py:807-817; kernels: cnf_toy_sample.hip) -------------------------
+// the argument errors of cnf_toy_sample that need no pointer but the descriptors (null: fine)
+static const char* toy_sample_desc_error(const cnf_toy_desc* d, int B, const cnf_toy_sample_desc* s) {
+    if (s == nullptr) return "null sample descriptor";
+    if (B < 1) return "B must be >= 1";
+    if (s->num_samples < 1) return "num_samples must be >= 1";
+    if (!(s->temperature >= 0.f) || std::isinf(s->temperature)) return "temperature must be finite and >= 0";
+    if (s->hist_bins < 0) return "hist_bins must be >= 0";
+    const int64_t tiles = ((int64_t)s->num_samples + TOY_SAMPLE_TS - 1) / TOY_SAMPLE_TS;
+    if ((int64_t)B * tiles > INT32_MAX || (double)B * s->num_samples * d->x_d > 4e18)
+        return "B * num_samples * x_d exceeds the index range (B * tiles must stay below 2^31)";
+    if (s->hist_bins >= 1) {
+        for (int c = 0; c < d->x_d; c++) {
+            if (!std::isfinite(s->hist_lo[c]) || !std::isfinite(s->hist_hi[c])) return "hist_lo / hist_hi must be finite";
+            if (!(s->hist_lo[c] < s->hist_hi[c])) return "hist_lo must be below hist_hi";
+            if (!std::isfinite((float)s->hist_bins / (s->hist_hi[c] - s->hist_lo[c]))) return "hist_lo / hist_hi: the bin scale is not finite";
+        }
+        if (std::pow((double)s->hist_bins, d->x_d) * B > 1e12) return "hist_bins: the grid exceeds 10^12 cells";
+    }
+    return nullptr;
+}
+
+static size_t toy_sample_part_bytes(const cnf_toy_desc* d, int B, const cnf_toy_sample_desc* s) {
+    const size_t tiles = ((size_t)s->num_samples + TOY_SAMPLE_TS - 1) / TOY_SAMPLE_TS;
+    return (size_t)B * tiles * d->x_d * TOY_SAMPLE_PART * sizeof(float);
+}
+
+size_t cnf_toy_sample_workspace_bytes(const cnf_toy_desc* d, int B, const cnf_toy_sample_desc* s) {
+    try {
+        toy_check(d);
+        if (const char* e = toy_sample_desc_error(d, B, s)) throw std::invalid_argument(e);
+        return toy_sample_part_bytes(d, B, s);
+    } catch (const std::exception& e) {
+        fail(CNF_E_INVALID, std::string("cnf_toy_sample_workspace_bytes: ") + e.what());
+        return 0;
+    }
+}
+
+int cnf_toy_sample(const cnf_toy_desc* d, const float* params, const float* y, const cnf_toy_sample_desc* s,
+                   float* samples, float* mean, float* std, float* y_dev, uint32_t* hist, void* workspace, int B,
+                   void* stream) {
+    CNF_TRY
+    toy_check(d);
+    if (!params || !workspace) return fail(CNF_E_INVALID, "cnf_toy_sample: null params or workspace");
+    if (!y) return fail(CNF_E_INVALID, "cnf_toy_sample: null y");
+    if (const char* e = toy_sample_desc_error(d, B, s)) return fail(CNF_E_INVALID, std::string("cnf_toy_sample: ") + e);
+    if (hist && s->hist_bins < 1) return fail(CNF_E_INVALID, "cnf_toy_sample: hist given with hist_bins < 1");
+    if (!hist && s->hist_bins >= 1) return fail(CNF_E_INVALID, "cnf_toy_sample: hist_bins >= 1 with a null hist");
+    if (!samples && !mean && !std && !y_dev && !hist)
+        return fail(CNF_E_INVALID, "cnf_toy_sample: no output requested (samples, mean, std, y_dev, hist all null)");
+    if (toy_sample_lds_bytes(d->intermediate_dims) > 160 * 1024)
+        return fail(CNF_E_INVALID, "cnf_toy_sample: the hidden activations of a draw tile exceed the 160 KiB LDS budget");
+    ToyArgs f;
+    toy_args(d, params, nullptr, nullptr, nullptr, nullptr, B, 1, f);
+    ToySampleArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.params = params;
+    a.y = y;
+    a.samples = samples;
+    a.y_dev = y_dev;
+    a.hist = hist;
+    a.part = static_cast<float*>(workspace);
+    a.B = B;
+    a.S = s->num_samples;
+    a.tiles = (s->num_samples + TOY_SAMPLE_TS - 1) / TOY_SAMPLE_TS;
+    a.nl = f.nl;
+    a.H = f.H;
+    a.L = f.L;
+    a.x_d = f.x_d;
+    a.HP = toy_bwd_hp(f.H);
+    a.temperature = s->temperature;
+    a.seed = s->seed;
+    a.offset = s->offset;
+    a.G = hist ? s->hist_bins : 0;
+    for (int c = 0; c < 2; c++) {
+        a.lo[c] = hist && c < f.x_d ? s->hist_lo[c] : 0.f;
+        a.scale[c] = hist && c < f.x_d ? (float)s->hist_bins / (s->hist_hi[c] - s->hist_lo[c]) : 0.f;
+    }
+    std::memcpy(a.order, f.order, sizeof(a.order));
+    std::memcpy(a.net_off, f.net_off, sizeof(a.net_off));
+    if (hist) {
+        size_t cells = (size_t)B;
+        for (int c = 0; c < f.x_d; c++) cells *= (size_t)s->hist_bins;
+        hip_check(hipMemsetAsync(hist, 0, cells * sizeof(uint32_t), (hipStream_t)stream), "hipMemsetAsync(hist)");
+    }
+    launch_toy_sample(a, (hipStream_t)stream);
+    hip_check(hipGetLastError(), "k_toy_sample");
+    if (mean || std) {
+        launch_toy_sample_stats(a.part, B, a.tiles, a.S, a.x_d, mean, std, (hipStream_t)stream);
+        hip_check(hipGetLastError(), "k_toy_sample_stats");
+    }
+    return CNF_OK;
+    CNF_CATCH
+}
+
 int cnf_toy_nll_sums(const float* per_sample, float* sums, int B, void* stream) {
     CNF_TRY
     if (!per_sample || !sums || B < 1) return fail(CNF_E_INVALID, "null pointer or empty batch");

@@ -5,7 +5,7 @@
 //                   reverse of the order the forward executed them. Per layer both nets (b, then A)
 //                   are recomputed from the layer input k_toy saved; a net's hidden activations
 //                   ((L+1) x TS x H) stay in LDS while it is back-propagated. The H x H Dense layers
-//                   run on v_mfma_f32_16x16x4_f32 (exact fp32 products): the recompute
+//                   run on v_mfma_f32_16x16x4_f32 (exact fp32 products; mma_tile, cnf_toy_mma.h): the recompute
 //                   [TS x H][H x H], the data gradient [TS x H][H x H]^T and the weight gradient
 //                   [(H+1) x TS][TS x H], whose row H is a row of ones (the bias gradient, which
 //                   follows the kernel in the canonical parameter order). The 1- and 2-wide first and
@@ -20,12 +20,11 @@
 #include <cstdint>
 
 #include "cnf_kernels.h"
+#include "cnf_toy_mma.h"
 
 namespace cnf {
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int TS = TOY_TS;
 constexpr int BT = 256;          // threads per workgroup (4 waves)
@@ -36,21 +35,6 @@ __device__ __forceinline__ float lrelu_f(float x) { return x >= 0.f ? x : LRELU_
 // LeakyReLU'(pre) from the stored post-activation value: h > 0 <=> pre > 0 (alpha > 0); 1 if pre > 0
 // else alpha, as TF
 __device__ __forceinline__ float lrelu_dh(float h) { return h > 0.f ? 1.f : LRELU_ALPHA; }
-
-// one 16x16 output tile of v_mfma_f32_16x16x4_f32 over K (a multiple of 4 after padding): lane l
-// supplies A[row l & 15][k = k0 + (l >> 4)] and B[k][col l & 15]; it receives
-// C[row 4 (l >> 4) + r][col l & 15] in element r. fa / fb return 0 outside the operand.
-template <class FA, class FB>
-__device__ __forceinline__ v4f mma_tile(int K, FA fa, FB fb, v4f acc) {
-    const int lane = threadIdx.x & 63;
-    const int rc = lane & 15, kq = lane >> 4;
-    for (int k0 = 0; k0 < K; k0 += 4) {
-        const float av = fa(rc, k0 + kq);
-        const float bv = fb(k0 + kq, rc);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-    }
-    return acc;
-}
 
 struct Net {
     const float* p;   // the net's parameters (global)

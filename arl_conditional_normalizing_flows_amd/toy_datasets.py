@@ -6,7 +6,11 @@ Reference semantics kept: two crescents (class 0: (cos a, sin a); class 1: (1 - 
 both coordinates, every column standardised with the float32 mean / std of one 10^4-per-crescent
 cloud on an even angle grid (:99-126), batched BEFORE shuffling so that a batch holds one class only
 (:265-267), and new points every epoch (the tf.data pipeline re-draws on each iteration; here the
-dataset is re-invoked per epoch by `training.fit`). The mixed and sector datasets are out of scope.
+dataset is re-invoked per epoch by `training.fit`).
+
+The sector datasets (`make_continuous_sectors`, `make_discrete_sectors`, :1114-1300) are the reference's data
+with a continuous condition: y is an angle, x a point of the unit disc's sector around it. The mixed dataset
+(`make_mixed_dataset`, its shape library) is out of scope.
 """
 from __future__ import annotations
 
@@ -60,3 +64,58 @@ class make_moons_dataset:
         xy = ((xy - self.mean) / self.std).reshape(2 * n, bs, 3)                   # batch, THEN shuffle
         order = torch.randperm(2 * n, generator=self._order).tolist()
         return iter([xy[i] for i in order])
+
+
+def _sector_rows(rng, y, sector_width):
+    """(r cos a, r sin a, y) per entry of y: a ~ U(y - width/2, y + width/2), r = sqrt(U(0, 1)), i.e. uniform
+    over the sector of the unit disc (TOYcINN_make_datasets.py:1152-1175); float32, not standardised (:1177)."""
+    ang = rng.uniform(y - sector_width / 2.0, y + sector_width / 2.0)
+    r = np.sqrt(rng.uniform(0.0, 1.0, y.shape))
+    return np.stack([r * np.cos(ang), r * np.sin(ang), y], axis=1).astype(np.float32)
+
+
+class make_continuous_sectors:
+    """`TOYcINN_make_datasets.make_continuous_sectors` (:1114-1205): each call returns the list of batches
+    [batch_size, 3] (the last one shorter when batch_size does not divide num_points) of (x0, x1, y) on
+    `device`: y ~ U[0, 2 pi) per point, x uniform over the sector of the unit disc centred on angle y with
+    angular width sector_width. New points every call, from a numpy generator seeded once."""
+
+    def __init__(self, num_points, batch_size, sector_width, seed=0, device=None):
+        self.num_points, self.batch_size = int(num_points), int(batch_size)
+        self.sector_width = float(sector_width)
+        if self.num_points < 1 or self.batch_size < 1:
+            raise ValueError('num_points and batch_size must be >= 1')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return (self.num_points + self.batch_size - 1) // self.batch_size
+
+    def __call__(self):
+        y = self._rng.uniform(0.0, 2.0 * math.pi, self.num_points)
+        # (a float64 draw just below 2 pi may round up to float32(2 pi), which is above it: keep y in [0, 2 pi))
+        y = np.minimum(y.astype(np.float32), np.nextafter(np.float32(2.0 * math.pi), np.float32(0.0))).astype(np.float64)
+        xy = torch.from_numpy(_sector_rows(self._rng, y, self.sector_width)).to(self.device)
+        return list(torch.split(xy, self.batch_size))
+
+
+class make_discrete_sectors:
+    """`TOYcINN_make_datasets.make_discrete_sectors` (:1207-1300): each call returns one batch
+    [num_points_per_sector, 3] per entry of which_sectors, in their order, with y that entry (as float32)."""
+
+    def __init__(self, num_points_per_sector, which_sectors, sector_width, seed=0, device=None):
+        self.num_points_per_sector = int(num_points_per_sector)
+        self.which_sectors = [float(np.float32(v)) for v in which_sectors]
+        self.sector_width = float(sector_width)
+        if self.num_points_per_sector < 1 or not self.which_sectors:
+            raise ValueError('num_points_per_sector must be >= 1 and which_sectors non-empty')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return len(self.which_sectors)
+
+    def __call__(self):
+        y = np.repeat(np.asarray(self.which_sectors, np.float64), self.num_points_per_sector)
+        xy = torch.from_numpy(_sector_rows(self._rng, y, self.sector_width)).to(self.device)
+        return list(torch.split(xy, self.num_points_per_sector))

@@ -2,7 +2,7 @@
 
 Same constructor arguments, `call(u, direction=-1)` / `log_loss` / `compile` / `train_step` /
 `test_step` / `metrics` semantics as TOYcINN_make_model.py:105-506, on torch tensors [B, 3] fp32 on the ROCm device; the
-flow runs in libcnf_hip.so (k_toy, and k_toy_bwd for the gradient) through the C ABI. Note the toy's direction convention is the
+flow runs in libcnf_hip.so (k_toy, k_toy_bwd for the gradient, k_toy_sample for `sample`) through the C ABI. Note the toy's direction convention is the
 reverse of cFlow's: -1 maps xy' -> zy (training direction, returns the per-sample log-det),
 +1 maps zy -> xy'.
 
@@ -138,6 +138,69 @@ class cINN_affine:
         return v, (ld if direction == -1 else 0)
 
     __call__ = call
+
+    def sample(self, y, num_samples, temperature=1.0, seed=0, offset=0, return_samples=True, return_stats=True,
+               return_y_dev=False, hist=None):
+        """num_samples draws of x given each condition y, their statistics and an optional histogram: what
+        the toy driver does once training ends (TOYcINN.py:807-817: z from the prior, concatenate y,
+        model(zy, direction=1); :823-... the cloud per condition) in one fused native call (cnf_toy_sample,
+        k_toy_sample: no [B*S, 3] tensor exists anywhere).
+
+        y: [B, 3 - x_d] on the device, or [3 - x_d] for one condition. The latent of condition b, draw s is
+        temperature * the N(0, 1) stream cnf_instance_noise writes into a [B, S, x_d] tensor at (seed, offset).
+        hist: None, or (G, lo, hi) with lo / hi scalars or one value per component: the draws counted on a grid
+        of G bins per component over [lo, hi), bin = floor((v - lo) * (G / (hi - lo))) in fp32.
+
+        Returns a dict with the requested ones of 'samples' [B, S, x_d], 'mean' and 'std' [B, x_d] (over the
+        draws, population form: np.std), 'y_dev' [B, S] (sum |y_hat - y| of each draw) and 'hist' (int32 counts,
+        [B, G] or [B, G, G] with component 0 major). With return_samples=False no [B, S, .] tensor is
+        allocated. The draws agree with call(zy, +1) up to rounding, not bit for bit (the hidden layers run on
+        the matrix cores); each draw's bits depend only on the weights, its y, seed, stream index and
+        temperature."""
+        y = _as_input(y, 'y')
+        yd = self.io_shape - self.x_d
+        if y.dim() == 1:
+            y = y.unsqueeze(0)
+        if y.dim() != 2 or y.shape[1] != yd:
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {yd}]')
+        B, S, x_d = int(y.shape[0]), int(num_samples), self.x_d
+        G, lo, hi = 0, (0.0, 0.0), (0.0, 0.0)
+        if hist is not None:
+            G, lo, hi = hist
+            G = int(G)
+            lo = tuple(float(v) for v in (lo if isinstance(lo, (tuple, list)) else (lo,) * x_d))
+            hi = tuple(float(v) for v in (hi if isinstance(hi, (tuple, list)) else (hi,) * x_d))
+            if len(lo) != x_d or len(hi) != x_d:
+                raise ValueError(f'hist lo / hi need one value per component ({x_d})')
+            if G < 1:
+                raise AssertionError('cINN_affine.sample: hist needs at least one bin')
+            lo, hi = lo + (0.0,) * (2 - x_d), hi + (0.0,) * (2 - x_d)
+        desc = _lib.cnf_toy_sample_desc(S, float(temperature), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                        G, (C.c_float * 2)(*lo), (C.c_float * 2)(*hi))
+        lib = _lib.load()
+        key = ('sample', B, S)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(lib.cnf_toy_sample_workspace_bytes(C.byref(self._desc), B, C.byref(desc)))
+            if nbytes <= 0:   # an argument error, as the reference's asserts
+                raise AssertionError(f'cINN_affine.sample: {lib.cnf_last_error().decode()}')
+            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+
+        def new(*shape, dtype=torch.float32):
+            return torch.empty(shape, device=y.device, dtype=dtype)
+        out = {}
+        if return_samples:
+            out['samples'] = new(B, S, x_d)
+        if return_stats:
+            out['mean'], out['std'] = new(B, x_d), new(B, x_d)
+        if return_y_dev:
+            out['y_dev'] = new(B, S)
+        if hist is not None:
+            out['hist'] = new(B, *([G] * x_d), dtype=torch.int32)
+        check(lib.cnf_toy_sample(C.byref(self._desc), ptr(self.params), ptr(y), C.byref(desc), ptr(out.get('samples')),
+                                 ptr(out.get('mean')), ptr(out.get('std')), ptr(out.get('y_dev')), ptr(out.get('hist')),
+                                 ptr(ws), B, _stream()), 'cnf_toy_sample')
+        return out
 
     def log_loss(self, xy, process_group=None):
         """(:419-451) -> (loss, -mean llz, -mean lly, -mean log_detJ); with process_group the 4 sums

@@ -348,6 +348,59 @@ int cnf_toy_forward_train(const cnf_toy_desc* d, const float* params, const floa
 int cnf_toy_backward(const cnf_toy_desc* d, const float* params, const float* xy, const float* zy,
                      void* train_workspace, int B, float inv_batch, float* dparams, void* stream);
 
+/* ---- TOYcINN sampling: S draws of x given y for each of B conditions, their mean / std and an
+ * optional histogram, in one fused launch. Replaces what the reference's toy driver does once
+ * training ends (TOYcINN.py:807-817: z from the prior, concatenate y, model(zy, direction=1);
+ * :823-... the cloud per condition), as cnf_flow_sample does for the image flow.
+ *
+ * Latent: the latent of condition b, draw s, component c < x_d is temperature * element
+ * offset + (b*S + s)*x_d + c of the seed's stream, i.e. what
+ * cnf_instance_noise(NULL, out, B*S*x_d, 0, seed, offset) writes into a [B,S,x_d] tensor, times
+ * temperature in one fp32 multiply; the remaining 3 - x_d components are y[b]. The flow runs in
+ * direction +1 (cnf_toy_call's law, u2 = (v2 - b) / exp(tanh A)); the H x H Dense layers run on
+ * the fp32 matrix cores, so the draws are cnf_toy_call's up to rounding (the same 1e-5 bound
+ * against the float64 model), not its bits. A draw's bits depend on (params, y[b], seed, its stream
+ * index, temperature) only: not on B, S, or which draws share its tile of 128.
+ *
+ * Outputs, each may be NULL but not all: samples [B][S][x_d]; mean, std [B][x_d] over the S draws
+ * (population form: divide by S, as np.std); y_dev [B][S] = sum over the 3 - x_d condition
+ * components of |y_hat - y|; hist, the counts on a grid (below).
+ *
+ * Statistics: draw s belongs to tile t = s / 128. Per tile and component the kernel folds, in draw
+ * order in fp32, the shifted partial (n_t, K_t, S1_t, S2_t): K_t the tile's first draw,
+ * S1_t = sum (v - K_t), S2_t = sum (v - K_t)^2. The partials are merged in tile order in fp64:
+ *   o_t = (K_t - K_0) + S1_t / n_t             the tile mean's offset from the first draw
+ *   q_t = max(0, S2_t - S1_t * (S1_t / n_t))   its centred second moment, about its own K_t
+ *   T = sum_t n_t o_t,  mean = K_0 + T / S
+ *   M2 = sum_t (q_t + n_t (o_t - T / S)^2),  std = sqrt(max(0, M2 / S))
+ * and rounded once to fp32. No atomics: the results are bitwise reproducible, and a tile's content
+ * is fixed by s alone.
+ *
+ * Histogram (hist_bins = G >= 1): uint32 hist[B][G] (x_d 1) or hist[B][G][G] (x_d 2, component 0
+ * major); bin_c = (int)floorf((v_c - hist_lo[c]) * scale_c) with scale_c = (float)G /
+ * (hist_hi[c] - hist_lo[c]) computed once in fp32. A draw is counted only if every component is
+ * finite and every bin_c lies in [0, G). The call zeroes hist itself on `stream`; counts are
+ * integer atomic adds, so they are exact and reproducible. */
+typedef struct cnf_toy_sample_desc {
+    int      num_samples;          /* S >= 1 draws per condition */
+    float    temperature;          /* >= 0, finite */
+    uint64_t seed, offset;         /* Philox stream, as cnf_instance_noise */
+    int      hist_bins;            /* 0: no histogram */
+    float    hist_lo[2], hist_hi[2];
+} cnf_toy_sample_desc;
+
+/* Workspace bytes of cnf_toy_sample: the partial slab [B][ceil(S / 128)][x_d] of 16 bytes each,
+ * whatever outputs are requested. 0 for an invalid argument (cnf_last_error says which). */
+size_t cnf_toy_sample_workspace_bytes(const cnf_toy_desc* d, int B, const cnf_toy_sample_desc* s);
+
+/* CNF_E_INVALID before any HIP call for: NULL y, params or workspace; B < 1 or S < 1; temperature
+ * negative or not finite; hist given with hist_bins < 1; hist_lo >= hist_hi or a non-finite edge;
+ * hist_bins >= 1 with hist NULL; no output requested; B * S * x_d beyond the index range (B *
+ * tiles must stay below 2^31). */
+int cnf_toy_sample(const cnf_toy_desc* d, const float* params, const float* y /* [B][3 - x_d] */,
+                   const cnf_toy_sample_desc* s, float* samples, float* mean, float* std,
+                   float* y_dev, uint32_t* hist, void* workspace, int B, void* stream);
+
 /* ---- input transforms (the step before the path; conv_cINN_base_functions.py) ----------- */
 
 /* Logit preprocessing of preprocess_dataset_class(LOGITS=True) (:174-231), elementwise over n
