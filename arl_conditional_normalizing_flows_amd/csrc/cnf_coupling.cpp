@@ -158,6 +158,8 @@ struct LnLoad {   // LayerNorm on load from the input's partials (slab.part == n
 struct Weights {   // packed image and bias in aux
     const float* w = nullptr;
     const float* b = nullptr;
+    const void* x6 = nullptr;   // the conv's bf16x6 plane image for k_pw (PackedConv::x6): x6_C K steps of x6_nr
+    int x6_C = 0, x6_nr = 0;    // column blocks; null: none
 };
 
 struct ProbSpec {
@@ -328,6 +330,12 @@ static int pw_launch(Exec& E, int role, ConvLaunch& cl, const std::vector<ProbSp
         q.in_mapped = x.in_map != nullptr ? 1 : 0;
         q.in_map = x.in_map;
         if (i < 2) q.out2 = x.out2[i];
+        // staging: a copy of the plan's plane image, or (debug option PRESPLIT=0) the split of the fp32 image
+        if (opts().presplit != 0) {
+            if (s.wt.x6 == nullptr || s.wt.x6_C != (s.in.c + 31) / 32 || s.wt.x6_nr != nr)
+                throw std::logic_error("k_pw launch: no plane image of this conv's K steps and column blocks in aux");
+            q.wx6 = s.wt.x6;
+        }
     }
     const bool lnf = probs[0].ln.slab.part != nullptr, resf = probs[0].res != nullptr, tapf = x.tap != nullptr;
     const int tiles = pw_tiles(a.H, a.W);
@@ -712,7 +720,10 @@ struct Streamed {
     LnLoad ln_load(int k, int n, const float* gamma, const float* beta) const {
         return ln ? LnLoad{sl[k][n], gamma, beta} : LnLoad{};
     }
-    Weights packed(const PackedConv& pc) const { return Weights{X + pc.w, X + pc.b}; }
+    Weights packed(const PackedConv& pc) const {
+        const bool pw6 = pc.x6 >= 0 && pc.fmt != PK_Q4;   // (a PK_Q4 branch's planes are k_gc's)
+        return Weights{X + pc.w, X + pc.b, pw6 ? X + pc.x6 : nullptr, pw6 ? pc.x6_C : 0, pw6 ? pc.nr : 0};
+    }
 
     // more slots than a consumer wave fetches in its prologue (64 x LN_FETCH = 512: the 128x128 layers):
     // merged once per image by k_ln_merge instead of by every consumer workgroup for each of its images
@@ -813,6 +824,10 @@ struct Streamed {
                 for (int k = 0; k < ng; k++) {
                     ga.w[n][k] = X + rb.gc[gg.br[k]].w;
                     ga.b[n][k] = X + rb.gc[gg.br[k]].b;
+                    if (opts().presplit != 0) {
+                        if (rb.gc[gg.br[k]].x6 < 0) throw std::logic_error("k_gc launch: branch without a plane image in aux");
+                        ga.w6[n][k] = X + rb.gc[gg.br[k]].x6;
+                    }
                 }
             }
             for (int bi : gg.br) done[bi] = 1;

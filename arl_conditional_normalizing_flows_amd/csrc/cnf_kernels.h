@@ -37,6 +37,7 @@ struct Options {
     int layout = 7;          // LAYOUT bits: 1 compact t1 sub-tensors, 2 mapped t2 sub-tensors, 4 polyphase k_gc tiles
     int fuse_coupling = 1;   // FUSE_COUPLING: 0 = every coupling layer launches its own k_coupling
     int lds_bwd = 2;         // LDS_BWD: 0 multi-kernel backward of the k_net_lds layers, 1 fused (one launch), 2 fused split
+    int presplit = 1;        // PRESPLIT: 0 = no bf16x6 plane image in aux, k_pw / k_gc split their fp32 weight images in every workgroup
     int train_alt = 0;       // TRAIN_ALT: a sum of the ALT_* bits below
     int train_sched = 0;     // TRAIN_SCHED: a sum of the SCHED_* bits below
     // SCHEDULE_CHECK: 1 = cnf_plan_create dry-runs the forward / inverse schedule and refuses a flow they
@@ -132,6 +133,7 @@ struct ConvProb {
     const int* in_map;                     // [quad][2]: input channel quad -> (offset of pixel 0 inside the image, pixel stride)
     float* out2;                           // k_pw only: also every output channel, plain [B][HW][cout] (null: none) —
                                            // the training forward's full t1 next to conv_a's mapped stores
+    const void* wx6;                       // k_pw only: the conv's bf16x6 plane image (x6_at; null: staged from wt)
 };
 
 struct ConvArgs {
@@ -287,6 +289,26 @@ inline void netshape_words(const NetLdsArgs& a, int* w) {
     for (int i = 0; i < NETSHAPE_W2; i++) w[NETSHAPE_W1 + i] = p2[i];
     w[NETSHAPE_MASK] = 0;
 }
+// The bf16x6 plane image of a conv's weights W[k][col] (cnf_stream.hip: what k_pw and k_gc keep in LDS, and
+// what the plan appends to aux per streamed conv so that staging is a copy): K in 32-deep steps c, NR
+// 16-column blocks nb, planes p = 0, 1, 2 (h, m, l of split3); 1 KiB per (c, p, nb), in which lane
+// (kq, i16) owns the 16 bytes of W[32c + 8kq + jj][16nb + i16], jj < 8. The one statement of the layout:
+// the plan's plane map and the kernels' fp32 staging both place an element with it.
+__host__ __device__ constexpr int x6_at(int k, int col, int p, int NR) {
+    return (((k >> 5) * 3 + p) * NR + (col >> 4)) * 1024 + ((((k >> 3) & 3) << 4) + (col & 15)) * 16 + (k & 7) * 2;
+}
+constexpr int64_t x6_bytes(int C, int NR) { return (int64_t)C * 3 * NR * 1024; }
+// k_gc's K-octet table (4 G entries of four ints, right behind a branch's planes in LDS and in aux): word j
+// of octet e (k = 8e .. 8e + 7, k = tap * S + ch) is the band offset, in bf16 elements from the pixel's
+// tap-(0, 0) origin, of the octet's j-th tap: one tap (S >= 8), two (S = 4) or four (S = 2); 0 for unused
+// words and past the 9 taps (their weights are zero: any in-band address is fine)
+__host__ __device__ constexpr int gc_octet_word(int S, int dil, int BW, int e, int j) {
+    const int per = S >= 8 ? 1 : 8 / S;
+    if (j >= per) return 0;
+    const int tap = S >= 8 ? 8 * e / S : per * e + j;
+    if (tap >= 9) return 0;
+    return ((tap / 3) * dil * BW + (tap % 3) * dil) * S + (S >= 8 ? 8 * e - tap * S : 0);
+}
 // k_gc (cnf_stream.hip): every grouped dilated branch of one residual block for a tile of TH
 // image rows of one net, `ipw` images per workgroup. Branch input windows are staged into LDS
 // bands with their own dilation halo (LN2 + LeakyReLU applied on the way in, zero padding), so
@@ -338,6 +360,7 @@ struct GcArgs {
     const float* beta[2];
     const float* w[2][GC_MAXBR];   // per k_gc branch (GcShape.br order)
     const float* b[2][GC_MAXBR];
+    const void* w6[2][GC_MAXBR];   // per branch: bf16x6 plane image + K-octet table (x6_at, gc_octet_word), or null: built from w
     GcShape s;                   // launch-independent part (compile-time in the shape-specialised kernels)
     int B, ipw, in_nparts, part_stride;
 };
@@ -496,6 +519,9 @@ void launch_chcopy(const float* in, int in_cs, int in_off, float* out, int out_c
 void launch_nll(const float* xy, const float* zy, const float* ld, float* per_image, float* sums, unsigned* done,
                 int B, int HW, int D, int x_d, float lambda_y, hipStream_t st);
 void launch_pack(const float* params, const int64_t* map, float* aux, long long n, hipStream_t st);
+// the bf16x6 plane region of aux, one 16-bit unit per map entry (Plan::x6_map): 4 * parameter + plane (the
+// plane's term of split3), -1: zero, <= -2: the literal -2 - entry (the K-octet tables' int halves)
+void launch_pack_x6(const float* params, const int64_t* map, void* dst, long long n, hipStream_t st);
 
 // ---- conditional sampling (cnf_sample.hip, cnf_flow_sample) -------------------------------------
 // One chunk of the B*S images of a sampling call: images g0 .. g0 + n - 1 of the flat [B][S] order

@@ -825,6 +825,32 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ params, 
     }
 }
 
+// the bf16x6 plane region of aux, one 16-bit unit per map entry: the plane's term of split3 (the split the
+// streamed kernels apply themselves under PRESPLIT=0), zero, or a literal
+__global__ __launch_bounds__(256) void k_pack_x6(const float* __restrict__ params, const int64_t* __restrict__ map,
+                                                 unsigned short* __restrict__ dst, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int64_t s = map[i];
+        unsigned short v = 0;
+        if (s >= 0) {
+            __bf16 t[3];
+            split3(params[s >> 2], t[0], t[1], t[2]);
+            const int p = (int)(s & 3);
+            v = __builtin_bit_cast(unsigned short, p == 0 ? t[0] : p == 1 ? t[1] : t[2]);
+        } else if (s <= -2) {
+            v = (unsigned short)(-2 - s);
+        }
+        dst[i] = v;
+    }
+}
+
+void launch_pack_x6(const float* params, const int64_t* map, void* dst, long long n, hipStream_t st) {
+    long long gx = (n + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    if (gx < 1) gx = 1;
+    CNF_LAUNCH(k_pack_x6, dim3((unsigned)gx), dim3(256), 0, st, params, map, reinterpret_cast<unsigned short*>(dst), n);
+}
+
 void launch_conv(int ks, int mr, int role, const ConvArgs& a, int grid_x, int lds, hipStream_t st) {
     dim3 g(grid_x, a.nprob), b(256);
 #define CNF_CONV_CASE(MR_, R_) \

@@ -855,6 +855,11 @@ ConvSrc columns_from(const ConvSrc& s, int c0) {
     return {[=](int k, int n) { return s.w(k, c0 + n); }, [=](int n) { return s.b(c0 + n); }};
 }
 
+// element s of quad qd (PK_Q4: channel quad tap * cin / 4 + cq; PK_1X1 / PK_TAP: input channels 4 qd .. + 3),
+// column j of a quad image [g][q][j][s], qd = 4g + q, of ns columns: the one statement of that layout (pack
+// writes with it, the plane image reads the fp32 image back with it)
+int64_t quad_at(int ns, int qd, int j, int s) { return ((int64_t)qd * ns + j) * 4 + s; }
+
 // kernel image (aux): a conv's weights + bias packed in its kernel's LDS layout (formats: PackedConv)
 void pack(Plan& p, PackedConv& pc, int fmt, int cin, int cout, const ConvSrc& s) {
     const int ks = p.desc.ksize;
@@ -868,33 +873,24 @@ void pack(Plan& p, PackedConv& pc, int fmt, int cin, int cout, const ConvSrc& s)
     pc.kpad = d.kpad;
     pc.size = d.size;
     pc.w = p.n_aux;
+    p.aux_map.resize(p.aux_map.size() + (size_t)pc.size, -1);
+    int64_t* img = p.aux_map.data() + pc.w;
     if (fmt == PK_Q4) {
         const int cpq = cin / 4, nq = 9 * cpq;
-        for (int g = 0; g < pc.G; g++)
-            for (int q = 0; q < 4; q++)
-                for (int j = 0; j < pc.ns; j++)
-                    for (int s4 = 0; s4 < 4; s4++) {
-                        const int qd = 4 * g + q;
-                        int64_t v = -1;
-                        if (qd < nq && j < cout) {
-                            const int tap = qd / cpq, cq = qd - tap * cpq;
-                            v = s.w(tap * cin + 4 * cq + s4, j);
-                        }
-                        p.aux_map.push_back(v);
-                    }
+        for (int qd = 0; qd < nq; qd++)
+            for (int j = 0; j < cout; j++)
+                for (int s4 = 0; s4 < 4; s4++) {
+                    const int tap = qd / cpq, cq = qd - tap * cpq;
+                    img[quad_at(pc.ns, qd, j, s4)] = s.w(tap * cin + 4 * cq + s4, j);
+                }
     } else if (fmt == PK_KN) {
         const int K = ks * ks * cin;
-        for (int k = 0; k < pc.kpad; k++)
-            for (int n = 0; n < pc.ns; n++) p.aux_map.push_back((k < K && n < cout) ? s.w(k, n) : -1);
+        for (int k = 0; k < K; k++)
+            for (int n = 0; n < cout; n++) img[(int64_t)k * pc.ns + n] = s.w(k, n);
     } else {
         const int ncol = (fmt == PK_TAP) ? 9 * cout : cout;
-        for (int g = 0; g < pc.G; g++)
-            for (int q = 0; q < 4; q++)
-                for (int j = 0; j < pc.ns; j++)
-                    for (int s4 = 0; s4 < 4; s4++) {
-                        const int c = 16 * g + 4 * q + s4;
-                        p.aux_map.push_back((c < cin && j < ncol) ? s.w(c, j) : -1);
-                    }
+        for (int c = 0; c < cin; c++)
+            for (int j = 0; j < ncol; j++) img[quad_at(pc.ns, c >> 2, j, c & 3)] = s.w(c, j);
     }
     p.n_aux += pc.size;
     pc.b = p.n_aux;
@@ -902,6 +898,84 @@ void pack(Plan& p, PackedConv& pc, int fmt, int cin, int cout, const ConvSrc& s)
     for (int n = 0; n < bpad; n++) p.aux_map.push_back(n < cout ? s.b(n) : -1);
     p.n_aux += bpad;
 }
+// ---- the bf16x6 plane image (debug option PRESPLIT) ---------------------------------------------------
+// One conv's planes appended to aux: C K steps of NR column blocks (cnf_kernels.h x6_at), element (k, col)
+// from the parameter that float at(k, col) of the fp32 kernel image holds (at < 0, or no parameter there:
+// zero). One x6_map entry per 16-bit unit.
+void plane_image(Plan& p, PackedConv& pc, int C, int NR, const std::function<int64_t(int, int)>& at) {
+    require(p.n_aux % 4 == 0, "plane image not 16-byte aligned");
+    pc.x6 = p.n_aux;
+    pc.x6_C = C;
+    const size_t base = p.x6_map.size();
+    p.x6_map.resize(base + (size_t)(x6_bytes(C, NR) / 2), -1);
+    for (int k = 0; k < 32 * C; k++)
+        for (int col = 0; col < 16 * NR; col++) {
+            const int64_t a = at(k, col);
+            const int64_t src = a >= 0 ? p.aux_map[(size_t)a] : -1;
+            if (src < 0) continue;
+            for (int pl = 0; pl < 3; pl++) p.x6_map[base + (size_t)x6_at(k, col, pl, NR) / 2] = 4 * src + pl;
+        }
+    p.n_aux += x6_bytes(C, NR) / 4;
+}
+constexpr int X6_DIR_WORDS = 16;
+// directory entry of the image just built: [kind (0 k_pw, 1 k_gc), coupling, net, role, residual block,
+// branch, x6, C, NR, fp32 image, ns, k_pw: G of the fp32 image / k_gc: cinp, cout, K rows with weights
+// (k_pw: cin; k_gc: S), dil, BW]
+void plane_dir(Plan& p, const PackedConv& pc, int kind, int ci, int net, int role, int rb, int bi, int NR, int g_or_cinp,
+               int krows, int dil, int BW) {
+    for (int64_t v : {(int64_t)kind, (int64_t)ci, (int64_t)net, (int64_t)role, (int64_t)rb, (int64_t)bi, pc.x6,
+                      (int64_t)pc.x6_C, (int64_t)NR, pc.w, (int64_t)pc.ns, (int64_t)g_or_cinp, (int64_t)pc.cout,
+                      (int64_t)krows, (int64_t)dil, (int64_t)BW})
+        p.x6_dir.push_back(v);
+}
+// a k_pw conv (PK_1X1 / PK_TAP image: rows k < 16 G, ns = 16 nr columns); k_pw runs K <= 128
+void pw_planes(Plan& p, PackedConv& pc, int ci, int net, int role, int rb, int bi) {
+    if (pc.size == 0 || pc.G > 8) return;
+    const PackedConv q = pc;
+    plane_image(p, pc, (pc.cin + 31) / 32, pc.nr,
+                [q](int k, int col) { return k < 16 * q.G ? q.w + quad_at(q.ns, k >> 2, col, k & 3) : (int64_t)-1; });
+    plane_dir(p, pc, 0, ci, net, role, rb, bi, pc.nr, pc.G, pc.cin, 0, 0);
+}
+// a k_gc branch (PK_Q4 image over cinp channels per tap): K index k = tap * S + ch (GcBranch), then its
+// K-octet table (gc_octet_word), 16 G ints as two literal 16-bit units each
+void gc_planes(Plan& p, PackedConv& pc, const GcBranch& g, int ci, int net, int rb, int bi) {
+    require(pc.fmt == PK_Q4 && pc.cin == g.cinp, "k_gc branch without a PK_Q4 image");
+    const PackedConv q = pc;
+    const int cpq = g.cinp / 4, S = g.S, cinp = g.cinp;
+    plane_image(p, pc, g.G, pc.nr, [q, cpq, S, cinp](int k, int col) {
+        const int tap = k / S, ch = k - tap * S;
+        return tap < 9 && ch < cinp ? q.w + quad_at(q.ns, tap * cpq + (ch >> 2), col, ch & 3) : (int64_t)-1;
+    });
+    for (int e = 0; e < 4 * g.G; e++)
+        for (int j = 0; j < 4; j++) {
+            const uint32_t w = (uint32_t)gc_octet_word(g.S, g.dil, g.BW, e, j);
+            p.x6_map.push_back(-2 - (int64_t)(w & 0xffffu));
+            p.x6_map.push_back(-2 - (int64_t)(w >> 16));
+        }
+    p.n_aux += 16 * g.G;
+    plane_dir(p, pc, 1, ci, net, ROLE_GC, rb, bi, pc.nr, g.cinp, g.S, g.dil, g.BW);
+}
+// Appends the plane images of every conv a streamed coupling's k_pw / k_gc launches can run, after all
+// fp32 images. Reads the PackedConvs' fp32 images (p.aux_map) and c.gcg; fills PackedConv::x6, p.x6_map,
+// p.x6_dir.
+void pack_planes(Plan& p, Coupling& c, int ci) {
+    if (c.use_lds) return;
+    for (int net = 0; net < 2; net++) {
+        NetParams& np = c.net[net];
+        pw_planes(p, np.ci_pw, ci, net, ROLE_CONV_IN, -1, -1);
+        for (size_t r = 0; r < np.rb.size(); r++) {
+            RBParams& rb = np.rb[r];
+            pw_planes(p, rb.ca, ci, net, ROLE_CONV_A, (int)r, -1);
+            for (const Coupling::GcGroup& gg : c.gcg)
+                for (size_t k = 0; k < gg.br.size(); k++)
+                    gc_planes(p, rb.gc[gg.br[k]], gg.gcb[k], ci, net, (int)r, gg.br[k]);
+            for (size_t bi = 0; bi < rb.gpw.size(); bi++) pw_planes(p, rb.gpw[bi], ci, net, ROLE_GC, (int)r, (int)bi);
+            pw_planes(p, rb.cb, ci, net, ROLE_CONV_B, (int)r, -1);
+        }
+        if (np.co.fmt == PK_TAP) pw_planes(p, np.co, ci, net, ROLE_CONV_OUT, -1, -1);
+    }
+}
+
 // dense backward image: a conv as [taps][cin][cout] + [cout] bias (training kernels)
 void dense_img(Plan& p, PackedConv& pc, int taps, int cin, int cout, const ConvSrc& s) {
     pc.taps = taps;
@@ -1127,6 +1201,17 @@ Plan* build_plan(const cnf_flow_desc* d) {
     p.aux_zero = p.n_aux;   // 128 zeros (bias of the bias-free tap GEMM, up to 80 columns)
     p.aux_map.resize(p.aux_map.size() + 128, -1);
     p.n_aux += 128;
+    p.x6_base = p.n_aux;
+    if (p.opts.presplit != 0) {
+        while (p.n_aux % 4 != 0) {   // (the plane images are copied 16 bytes at a time)
+            p.aux_map.push_back(-1);
+            p.n_aux++;
+        }
+        p.x6_base = p.n_aux;
+        for (size_t ci = 0; ci < p.couplings.size(); ci++) pack_planes(p, p.couplings[ci], (int)ci);
+        p.aux_map.resize((size_t)p.n_aux, -1);   // (no fp32 entries there: k_pack stops at x6_base)
+    }
+    require((int64_t)p.x6_map.size() == 2 * (p.n_aux - p.x6_base), "plane map out of step with the plane region");
     require(p.n_params < (1ll << 31) && p.n_aux < (1ll << 31), "parameter image exceeds 2^31 floats");
     require(p.n_bw < (1ll << 31), "dense backward image exceeds 2^31 floats");
     for (auto& c : p.couplings) offset_tables(c);

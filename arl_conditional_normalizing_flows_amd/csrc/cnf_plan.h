@@ -40,6 +40,10 @@ struct PackedConv {
     // training: offsets into the dense backward image (bw image): [taps][cin][cout] weights, [cout] bias
     int64_t dw = -1, db = -1;
     int taps = 9;
+    // streamed layers: the conv's bf16x6 plane image (cnf_kernels.h x6_at) in aux, as a float offset (a multiple
+    // of 4; -1: none) -- a k_pw conv's x6_C K steps of nr column blocks, a k_gc branch's planes and K-octet table
+    int64_t x6 = -1;
+    int x6_C = 0;
 };
 
 struct RBParams {
@@ -289,6 +293,12 @@ struct Plan {
     int64_t n_aux = 0;
     int64_t aux_zero = 0;           // offset of 128 zero floats in the kernel image
     std::vector<int64_t> aux_map;   // kernel image: aux[i] = params[aux_map[i]] (or 0 if < 0)
+    // the bf16x6 plane region of aux, floats [x6_base, n_aux) (x6_base == n_aux: none, debug option PRESPLIT=0;
+    // aux_map is -1 there): one x6_map entry per 16-bit unit, 4 * parameter + plane, -1 zero, <= -2 the literal
+    // -2 - entry; x6_dir: X6_DIR_WORDS words per image (cnf_plan_weight_map, which = 3)
+    int64_t x6_base = 0;
+    std::vector<int64_t> x6_map, x6_dir;
+    int64_t* dev_x6_map = nullptr;
     // training: dense backward image bw[i] = params[bw_map[i]] (0 if < 0); the same map scatters
     // dense weight gradients back onto the canonical parameters
     std::vector<int64_t> bw_map;

@@ -78,7 +78,8 @@ Options parse_options(const char* s) {
                                    {"PW", &Options::pw},                   {"GENERIC", &Options::generic},
                                    {"LAYOUT", &Options::layout},           {"FUSE_COUPLING", &Options::fuse_coupling},
                                    {"LDS_BWD", &Options::lds_bwd},         {"TRAIN_ALT", &Options::train_alt},
-                                   {"TRAIN_SCHED", &Options::train_sched}, {"SCHEDULE_CHECK", &Options::schedule_check}};
+                                   {"TRAIN_SCHED", &Options::train_sched}, {"SCHEDULE_CHECK", &Options::schedule_check},
+                                   {"PRESPLIT", &Options::presplit}};
     std::string str(s);
     size_t pos = 0;
     while (pos < str.size()) {
@@ -102,6 +103,7 @@ Options parse_options(const char* s) {
         if (!found) throw std::invalid_argument("debug_options: unknown option '" + key + "'");
     }
     if (o.lds_bwd < 0 || o.lds_bwd > 2) throw std::invalid_argument("debug_options: LDS_BWD is 0, 1 or 2");
+    if (o.presplit < 0 || o.presplit > 1) throw std::invalid_argument("debug_options: PRESPLIT is 0 or 1");
     return o;
 }
 
@@ -185,11 +187,17 @@ static void ensure_tables(Plan& p) {
     if (!p.host_table.empty())
         hip_check(hipMemcpy(p.dev_table, p.host_table.data(), p.host_table.size() * sizeof(int), hipMemcpyHostToDevice),
                   "hipMemcpy(table)");
-    size_t na = std::max<size_t>(1, p.aux_map.size()) * sizeof(int64_t);
+    // (the fp32 part of the kernel image: the plane region behind it has a map of its own)
+    size_t na = std::max<size_t>(1, (size_t)p.x6_base) * sizeof(int64_t);
     hip_check(hipMalloc(&p.dev_aux_map, na), "hipMalloc(aux map)");
-    if (!p.aux_map.empty())
-        hip_check(hipMemcpy(p.dev_aux_map, p.aux_map.data(), p.aux_map.size() * sizeof(int64_t), hipMemcpyHostToDevice),
+    if (p.x6_base > 0)
+        hip_check(hipMemcpy(p.dev_aux_map, p.aux_map.data(), (size_t)p.x6_base * sizeof(int64_t), hipMemcpyHostToDevice),
                   "hipMemcpy(aux map)");
+    size_t nx = std::max<size_t>(1, p.x6_map.size()) * sizeof(int64_t);
+    hip_check(hipMalloc(&p.dev_x6_map, nx), "hipMalloc(plane map)");
+    if (!p.x6_map.empty())
+        hip_check(hipMemcpy(p.dev_x6_map, p.x6_map.data(), p.x6_map.size() * sizeof(int64_t), hipMemcpyHostToDevice),
+                  "hipMemcpy(plane map)");
     size_t nbw = std::max<size_t>(1, p.bw_map.size()) * sizeof(int64_t);
     hip_check(hipMalloc(&p.dev_bw_map, nbw), "hipMalloc(bw map)");
     if (!p.bw_map.empty())
@@ -255,6 +263,7 @@ void cnf_plan_destroy(cnf_plan* plan) {
     if (plan->p) {
         if (plan->p->dev_table) (void)hipFree(plan->p->dev_table);
         if (plan->p->dev_aux_map) (void)hipFree(plan->p->dev_aux_map);
+        if (plan->p->dev_x6_map) (void)hipFree(plan->p->dev_x6_map);
         if (plan->p->dev_bw_map) (void)hipFree(plan->p->dev_bw_map);
         for (hipEvent_t e : plan->p->ev) (void)hipEventDestroy(e);
         if (plan->p->ev_fork) (void)hipEventDestroy(plan->p->ev_fork);
@@ -331,7 +340,10 @@ int cnf_pack_params(cnf_plan* plan, const float* params, float* aux, void* strea
     CNF_TRY
     Plan& p = *plan->p;
     ensure_tables(p);
-    if (p.n_aux > 0) launch_pack(params, p.dev_aux_map, aux, (long long)p.n_aux, (hipStream_t)stream);
+    if (p.x6_base > 0) launch_pack(params, p.dev_aux_map, aux, (long long)p.x6_base, (hipStream_t)stream);
+    // the streamed convs' bf16x6 planes (and k_gc's K-octet tables): split here, once per weight update
+    if (!p.x6_map.empty())
+        launch_pack_x6(params, p.dev_x6_map, aux + p.x6_base, (long long)p.x6_map.size(), (hipStream_t)stream);
     check_launch();
     return CNF_OK;
     CNF_CATCH
@@ -1386,8 +1398,9 @@ int cnf_plan_launch_time_ms(const cnf_plan* plan, int i, float* ms) {
 
 int64_t cnf_plan_weight_map(const cnf_plan* plan, int which, int64_t* out, int64_t cap) {
     OptScope os_(plan ? &plan->p->opts : nullptr);
-    if (!plan || (which != 0 && which != 1)) return fail(CNF_E_INVALID, "null plan or which not in {0, 1}");
-    const std::vector<int64_t>& m = which == 0 ? plan->p->aux_map : plan->p->bw_map;
+    if (!plan || which < 0 || which > 3) return fail(CNF_E_INVALID, "null plan or which not in {0, 1, 2, 3}");
+    const Plan& pl = *plan->p;
+    const std::vector<int64_t>& m = which == 0 ? pl.aux_map : which == 1 ? pl.bw_map : which == 2 ? pl.x6_map : pl.x6_dir;
     if (out)
         for (int64_t i = 0; i < std::min<int64_t>(cap, (int64_t)m.size()); i++) out[i] = m[i];
     return (int64_t)m.size();

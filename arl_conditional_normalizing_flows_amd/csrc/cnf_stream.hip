@@ -14,8 +14,9 @@
 //
 // The contraction runs on the bf16 matrix cores as the exact three-term split of cnf_device.h
 // (bf16x6, fp32-accurate): K in 32-deep steps, lane (i16, kq) of a wave holding channels
-// 32c + 8kq .. +7 of its pixel at step c; the weights are staged once per workgroup as their three
-// bf16 planes (stage_w_x6).
+// 32c + 8kq .. +7 of its pixel at step c; the weights lie in LDS as their three bf16 planes (x6_at),
+// copied once per workgroup from the plane image cnf_pack_params built (stage_copy16), or, under the
+// debug option PRESPLIT=0, split from the fp32 image by the workgroup itself (stage_w_x6).
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -86,7 +87,7 @@ __device__ __forceinline__ void stage_w_x6(const float* __restrict__ src, unsign
             const int k0 = 32 * c + 8 * (ln >> 4) + 4 * half, col = 16 * nb + (ln & 15);
             const int g = k0 >> 4, q = (k0 >> 2) & 3;
             v[u] = t < n && g < G ? s4[(g * 4 + q) * NSJ + col] : f4{0.f, 0.f, 0.f, 0.f};
-            o[u] = t < n ? (c * 3 * NR + nb) * 1024 + ln * 16 + half * 8 : -1;
+            o[u] = t < n ? x6_at(k0, col, 0, NR) : -1;   // plane 0; planes 1, 2 follow NR KiB apart
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -96,6 +97,34 @@ __device__ __forceinline__ void stage_w_x6(const float* __restrict__ src, unsign
             *reinterpret_cast<bf16x4*>(dst + o[u]) = h;
             *reinterpret_cast<bf16x4*>(dst + o[u] + NR * 1024) = m;
             *reinterpret_cast<bf16x4*>(dst + o[u] + 2 * NR * 1024) = l;
+        }
+    }
+}
+
+// Staging from the plan's bf16x6 plane image (cnf_kernels.h x6_at; built once per weight update by
+// cnf_pack_params): the image is byte for byte what stage_w_x6 / stage_gcw_x6 leave in LDS, so the
+// workgroup copies its n16 16-byte units, unit tid + u NTH by thread tid. MAXU > 0: a compile-time bound
+// on the units per thread, every load in flight before the first LDS write (units past n16 read 0 through
+// the buffer resource and are not written); MAXU == 0 (run-time shapes): sweeps of four units per thread
+template <int NTH, int MAXU>
+__device__ __forceinline__ void stage_copy16(const void* __restrict__ src, unsigned char* dst, int n16) {
+    const auto r = buf_rsrc(src, (uint32_t)n16 * 16u);
+    const int tid = (int)threadIdx.x;
+    if constexpr (MAXU > 0) {
+        f4 v[MAXU];
+#pragma unroll
+        for (int u = 0; u < MAXU; u++) v[u] = buf_load4(r, (uint32_t)(tid + u * NTH) * 16u);
+#pragma unroll
+        for (int u = 0; u < MAXU; u++)
+            if (tid + u * NTH < n16) *reinterpret_cast<f4*>(dst + (tid + u * NTH) * 16) = v[u];
+    } else {
+        for (int base = 0; base < n16; base += NTH * 4) {
+            f4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) v[u] = buf_load4(r, (uint32_t)(base + tid + u * NTH) * 16u);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (base + tid + u * NTH < n16) *reinterpret_cast<f4*>(dst + (base + tid + u * NTH) * 16) = v[u];
         }
     }
 }
@@ -253,7 +282,10 @@ __global__ __launch_bounds__(64 * PW_NW, CNF_PW_MINW) void k_pw(ConvArgs a) {
     const bool lnpre = LN && wave < nimg;   // (image wave: the LN table below is per workgroup)
     const LnSlots slot0 = lnpre ? in_ln_fetch(P, img0 + wave) : LnSlots{};
     // weights -> their bf16x6 planes in LDS; per-image input LN (mean, rstd) -> LDS
-    stage_w_x6<64 * NW, NR>(P.wt, lwb, G, C);
+    if (P.wx6 != nullptr)   // (CM K steps at most: C <= CM)
+        stage_copy16<64 * NW, (CM * 3 * NR * 64 + 64 * NW - 1) / (64 * NW)>(P.wx6, lwb, C * 3 * NR * 64);
+    else
+        stage_w_x6<64 * NW, NR>(P.wt, lwb, G, C);
     if (LN) {
         for (int i = wave; i < nimg; i += NW) {
             float mu, rs;
@@ -471,6 +503,15 @@ __device__ __forceinline__ int gc_out_pixel(const GcArgs& a, int po, int px0, in
     return px0 + por * GS(W) + poc;
 }
 
+// 16-byte units of a branch's planes and K-octet table (contiguous in LDS from w_off, and in the plan's
+// plane image), and the most a thread of an nt-thread workgroup copies of any branch of s
+__host__ __device__ constexpr int gc_w16(const GcBranch& br) { return br.G * 3 * ((br.cout + 15) >> 4) * 64 + 4 * br.G; }
+constexpr int gc_copy_units(const GcShape& s, int nt) {
+    int m = 1;
+    for (int bi = 0; bi < s.nbr; bi++) m = (gc_w16(s.br[bi]) + nt - 1) / nt > m ? (gc_w16(s.br[bi]) + nt - 1) / nt : m;
+    return m;
+}
+
 // The branch's PK_Q4 fp32 weight image (plan: quads qd = tap * cinp / 4 + ch / 4, [qd][16 nr][4]) ->
 // its bf16x6 planes in LDS (as k_pw's stage_w_x6, rows = outputs): lane (kq, i16) of K step c, output
 // block nb holds W[k = 32c + 8kq + jj][16nb + i16], k = tap * S + ch; zero past the taps / channels
@@ -493,7 +534,7 @@ __device__ __forceinline__ void stage_gcw_x6(const float* __restrict__ src, unsi
                               ? src[((tap * cpq4 + (ch >> 2)) * ns + col) * 4 + (ch & 3)]
                               : 0.f;
             }
-            o[u] = t < n ? (c * 3 * nr + nb) * 1024 + ln * 16 + half * 8 : -1;
+            o[u] = t < n ? x6_at(k0, col, 0, nr) : -1;
         }
 #pragma unroll
         for (int u = 0; u < 2; u++) {
@@ -834,33 +875,47 @@ __global__ __launch_bounds__(GC_NTS, SID >= 0 ? 16 / GC_NWS : 1) void k_gc(GcArg
     lnP.part_stride = a.part_stride;
     const bool lnpre = ln && wave < nimg;
     const LnSlots slot0 = lnpre ? in_ln_fetch(lnP, img0 + wave) : LnSlots{};
-    // weight planes, biases and K-octet offset tables of every branch (once per workgroup)
+    // weight planes, biases and K-octet offset tables of every branch (once per workgroup). From the
+    // plan's plane image (a.w6: planes, then the table, as they lie in LDS from w_off on), copied with every
+    // branch's loads in flight before the first LDS write; or (debug option PRESPLIT=0, a.w6 null) split
+    // from the fp32 image, the table computed
+    if (a.w6[net][0] != nullptr) {
+        if constexpr (SID >= 0) {
+            constexpr int NBR = kGcShapes[SID >= 0 ? SID : 0].nbr, MU = gc_copy_units(kGcShapes[SID >= 0 ? SID : 0], GC_NT);
+            f4 wv[NBR][MU];
+#pragma unroll
+            for (int bi = 0; bi < NBR; bi++) {
+                const int n16 = gc_w16(GS(br)[bi]);
+                const auto r = buf_rsrc(a.w6[net][bi], (uint32_t)n16 * 16u);
+#pragma unroll
+                for (int u = 0; u < MU; u++)
+                    if (u * GC_NT < n16) wv[bi][u] = buf_load4(r, (uint32_t)(tid + u * GC_NT) * 16u);
+            }
+#pragma unroll
+            for (int bi = 0; bi < NBR; bi++) {
+                const int n16 = gc_w16(GS(br)[bi]);
+#pragma unroll
+                for (int u = 0; u < MU; u++)
+                    if (u * GC_NT < n16 && tid + u * GC_NT < n16)
+                        *reinterpret_cast<f4*>(smem + GS(br)[bi].w_off + (tid + u * GC_NT) * 16) = wv[bi][u];
+            }
+        } else {
+            for (int bi = 0; bi < GS(nbr); bi++)
+                stage_copy16<GC_NT, 0>(a.w6[net][bi], smem + GS(br)[bi].w_off, gc_w16(GS(br)[bi]));
+        }
+    } else {
+        for (int bi = 0; bi < GS(nbr); bi++) {
+            const GcBranch& br = GS(br)[bi];
+            stage_gcw_x6<GC_NT>(a.w[net][bi], smem + br.w_off, br, (br.cout + 15) >> 4);
+            int4* ot = reinterpret_cast<int4*>(smem + br.q_off);
+            for (int e = tid; e < 4 * br.G; e += GC_NT)
+                ot[e] = make_int4(gc_octet_word(br.S, br.dil, br.BW, e, 0), gc_octet_word(br.S, br.dil, br.BW, e, 1),
+                                  gc_octet_word(br.S, br.dil, br.BW, e, 2), gc_octet_word(br.S, br.dil, br.BW, e, 3));
+        }
+    }
     for (int bi = 0; bi < GS(nbr); bi++) {
         const GcBranch& br = GS(br)[bi];
-        const int nr = (br.cout + 15) >> 4;
-        stage_gcw_x6<GC_NT>(a.w[net][bi], smem + br.w_off, br, nr);
         for (int i = tid; i < br.cout; i += GC_NT) reinterpret_cast<float*>(smem + br.b_off)[i] = a.b[net][bi][i];
-        // K octet e: k = 8e .. 8e + 7, k = tap * S + ch: the band offsets (bf16 elements from the pixel's
-        // tap-(0, 0) origin) of its one (S >= 8), two (S = 4) or four (S = 2) taps; past the 9 taps: 0
-        // (their weights are zero: any in-band address is fine)
-        int4* ot = reinterpret_cast<int4*>(smem + br.q_off);
-        auto tapo = [&](int tap) { return tap < 9 ? (((tap / 3) * br.dil) * br.BW + (tap % 3) * br.dil) * br.S : 0; };
-        for (int e = tid; e < 4 * br.G; e += GC_NT) {
-            int4 o = {0, 0, 0, 0};
-            if (br.S >= 8) {
-                const int t = 8 * e / br.S;
-                o.x = t < 9 ? tapo(t) + 8 * e - t * br.S : 0;
-            } else if (br.S == 4) {
-                o.x = tapo(2 * e);
-                o.y = tapo(2 * e + 1);
-            } else {
-                o.x = tapo(4 * e);
-                o.y = tapo(4 * e + 1);
-                o.z = tapo(4 * e + 2);
-                o.w = tapo(4 * e + 3);
-            }
-            ot[e] = o;
-        }
     }
     GSTAMP(gs++);   // (diagnostic builds: band / gamma / beta / weight loads landed)
     // per-image LN2 (mean, rstd) from the producer's partials

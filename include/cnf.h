@@ -77,7 +77,7 @@ typedef struct cnf_flow_desc {
     int group_mode;                       /* CNF_GROUP_* (default REFERENCE) */
     /* Debug options, NULL or "" for the defaults (what is benchmarked): "NAME=V[,NAME=V...]" selecting
      * the alternative code paths the parity tests compare against — NETLDS, GC, PW, GENERIC, LAYOUT,
-     * FUSE_COUPLING, LDS_BWD, TRAIN_ALT, TRAIN_SCHED, SCHEDULE_CHECK (meanings: csrc/cnf_kernels.h Options). Parsed at
+     * FUSE_COUPLING, LDS_BWD, TRAIN_ALT, TRAIN_SCHED, SCHEDULE_CHECK, PRESPLIT (meanings: csrc/cnf_kernels.h Options). Parsed at
      * cnf_plan_create (unknown name: CNF_E_INVALID); the string is not kept. Without a GENERIC entry, a
      * flow on images of 64 x 64 and above runs the generic k_pw / k_gc kernels (GENERIC=6; the
      * shape-specialised ones showed intermittent differences there). The library reads no
@@ -455,8 +455,14 @@ int cnf_nll_allreduce(cnf_comm* comm, const float* sums, int B, float* red5, voi
 /* Plan introspection (tests): the canonical parameter index behind every float
  * of the kernel image (which = 0; -1 = zero padding; cnf_pack_params computes
  * aux[i] = params[map[i]]) or of the dense training image (which = 1: every
- * conv as [taps][cin][cout] + bias padded to 4, in layer order). Returns the
- * map length; copies min(length, cap) entries when out != NULL. */
+ * conv as [taps][cin][cout] + bias padded to 4, in layer order). which = 2:
+ * the bf16x6 plane region at the end of the kernel image (the streamed convs'
+ * weights as k_pw / k_gc keep them in LDS, built unless PRESPLIT=0; which = 0
+ * is -1 over it), one entry per 16-bit unit: 4 * parameter + plane (0, 1, 2 =
+ * the h, m, l terms of the parameter's exact bf16 split), -1 = zero, <= -2 =
+ * the literal value -2 - entry. which = 3: its directory, 16 words per conv
+ * (DESIGN.md section 4). Returns the map length; copies min(length, cap)
+ * entries when out != NULL. */
 int64_t cnf_plan_weight_map(const cnf_plan* plan, int which, int64_t* out, int64_t cap);
 
 /* Measurement hooks (bench.py): number of kernel launches recorded by the last
