@@ -73,10 +73,14 @@ _SIGS = [
     ('cnf_flow_forward_noise', C.c_int, [_P, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_uint64, _F, _F, _F, _P,
                                          C.c_int, _P]),
     ('cnf_flow_inverse', C.c_int, [_P, _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_flow_inverse_logdet', C.c_int, [_P, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_plan_sample_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_sample_desc)]),
     ('cnf_flow_sample', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_flow_sample_logp', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), _F, _F, _F, _F, _F, _P, C.c_int,
+                                       _P]),
     ('cnf_coupling_forward', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_coupling_inverse_logdet', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_squeeze', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_channel_copy', C.c_int, [_F, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, _P]),

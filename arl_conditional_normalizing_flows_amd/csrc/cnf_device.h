@@ -186,6 +186,27 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// Sum of image img's log-det partial slots part[((l * B) + img) * np + j] over nl layers and np parts, by
+// one wave: lane k folds entries k, k + 64, ... (four loads in flight together), then the fixed-order wave
+// sum. The one summation order of every per-image log-det total (k_ld_reduce, k_sample_logp).
+__device__ __forceinline__ double ld_slot_sum(const double* __restrict__ part, int B, int img, int nl, int np,
+                                              int lane) {
+    const int n = nl * np;
+    double s = 0.0;
+    for (int k0 = 0; k0 < n; k0 += 256) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int k = k0 + 64 * u + lane;
+            const int l = k / np, j = k - l * np;
+            v[u] = k < n ? part[((size_t)l * B + img) * np + j] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) s += v[u];
+    }
+    return wave_sum(s);
+}
+
 __device__ __forceinline__ bool stored(const ConvProb& P, int ch) {
     return ((ch < 32 ? (P.st_mask_lo >> ch) : (P.st_mask_hi >> (ch - 32))) & 1u) != 0u;
 }

@@ -198,7 +198,8 @@ struct CoupPend {
     int comp = 0, mask = 0, dc1 = 0;
     int W = 0, D = 0;   // u_k's width and depth (k_map2 applies a pending coupling of the last layer of a block)
     // +1: the forward law v2 = exp(s) u2 + t (ld_part collects layer k's sum of s); -1: the inverse
-    // law u2 = (1 / exp(s)) (v2 - t) of cnf_flow_inverse (ld_part null). In the inverse schedule
+    // law u2 = (1 / exp(s)) (v2 - t) of cnf_flow_inverse (ld_part null) / cnf_flow_inverse_logdet
+    // (ld_part collects the same sum of s; the reduction negates it). In the inverse schedule
     // "layer k" is the layer just run and "k+1" the one before it in index order, run next.
     int dir = 1;
 };
@@ -473,7 +474,9 @@ void launch_convtap(int mt, bool vec, const ConvArgs& a, int grid_x, int lds, hi
 void launch_gather_u1c(const float* u, float* u1c, int B, int H, int W, int D, int mask, int hc, int wc, int dc1,
                        hipStream_t st);
 void launch_coupling(const CoupArgs& a, int B, int nparts, hipStream_t st);
-void launch_ld_reduce(const double* part, float* out, int B, int nl, int np, int accumulate, hipStream_t st);
+// out[img] (accumulate: +=) the sum of image img's slots part[nl][B][np]; negate: minus the sum
+void launch_ld_reduce(const double* part, float* out, int B, int nl, int np, int accumulate, hipStream_t st,
+                      int negate = 0);
 // LN partial slots [B][part_stride][LNP] of one tensor (two nets: part0, part1 or null) merged into
 // slot 0 of each image (k_ln_merge): consumers then read nparts = 1
 void launch_ln_merge(float* part0, float* part1, int nparts, int part_stride, int B, hipStream_t st);
@@ -554,6 +557,11 @@ void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream
 // k_sample_ydev: y_dev[g0 + i] = sum_{p, c >= x_d} |xy_hat[i, p, c] - y[(g0 + i) / S, p, c - x_d]|, one
 // wave per image, fp64 lane sums in element order then a fixed-order wave sum
 void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st);
+// k_sample_logp: log_prob[g0 + i] = (float)(-0.5 q - 0.5 n log(2 pi) + L), n = HW * x_d, q the fp64 sum of
+// z^2 over image i's latent (channels < x_d of the chunk's zy), L the fp64 sum of image i's log-det slots
+// ld_part[nl][c.n][np] as the chunk's inverse wrote them (k_ld_reduce's order); one wave per image
+void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
+                        hipStream_t st);
 
 
 // ---- training (cnf_train.hip) -------------------------------------------------------------------

@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256) void k_coupling(CoupArgs a) {
             }
             const float s = w * cpl_tanh(sp);
             vb[q] = cpl_law(s, ub[q], t, a.dir);   // (k_net_lds / k_map2 apply a deferred coupling with the same expression)
-            if (a.dir > 0) lsum += s;
+            lsum += s;   // (either direction: the inverse's log-det is minus this sum)
         } else {
             const int e1 = e - n2;
             const int p = e1 / a.dc1, c = e1 - p * a.dc1;
@@ -574,25 +574,14 @@ __global__ __launch_bounds__(256) void k_ln_merge(float* __restrict__ part0, flo
     }
 }
 
-// out[img] (=|+=) sum over nl layers, np parts of part[((l*B)+img)*np + j]: one wave per image,
+// out[img] (=|+=|-=) sum over nl layers, np parts of part[((l*B)+img)*np + j]: one wave per image,
 // lane k folds entries k, k+64, ... (all its loads in flight together), then a fixed-order wave sum
+// (ld_slot_sum); negate: minus the sum (the inverse's log-det)
 __global__ __launch_bounds__(64) void k_ld_reduce(const double* __restrict__ part, float* __restrict__ out, int B,
-                                                  int nl, int np, int accumulate) {
+                                                  int nl, int np, int accumulate, int negate) {
     const int img = blockIdx.x, lane = threadIdx.x;
-    const int n = nl * np;
-    double s = 0.0;
-    for (int k0 = 0; k0 < n; k0 += 256) {
-        double v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int k = k0 + 64 * u + lane;
-            const int l = k / np, j = k - l * np;
-            v[u] = k < n ? part[((size_t)l * B + img) * np + j] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) s += v[u];
-    }
-    s = wave_sum(s);
+    double s = ld_slot_sum(part, B, img, nl, np, lane);
+    if (negate) s = -s;
     if (lane == 0) out[img] = accumulate ? (float)((double)out[img] + s) : (float)s;
 }
 
@@ -930,8 +919,9 @@ void launch_ln_merge(float* part0, float* part1, int nparts, int part_stride, in
     CNF_LAUNCH(k_ln_merge, dim3(B, part1 != nullptr ? 2 : 1), dim3(256), 0, st, part0, part1, nparts, part_stride);
 }
 
-void launch_ld_reduce(const double* part, float* out, int B, int nl, int np, int accumulate, hipStream_t st) {
-    CNF_LAUNCH(k_ld_reduce, dim3(B), dim3(64), 0, st, part, out, B, nl, np, accumulate);
+void launch_ld_reduce(const double* part, float* out, int B, int nl, int np, int accumulate, hipStream_t st,
+                      int negate) {
+    CNF_LAUNCH(k_ld_reduce, dim3(B), dim3(64), 0, st, part, out, B, nl, np, accumulate, negate);
 }
 
 void launch_map_gather(const float* src, float* dst, const int* idx, int n, int ss, int ds, int B, hipStream_t st) {

@@ -1306,7 +1306,7 @@ __global__ __launch_bounds__(NT) void k_net_lds(NetLdsArgs a) {
         const double ws = wave_sum((double)lsum);
         if ((threadIdx.x & 63) == 0) lsl[threadIdx.x >> 6] = ws;
         lds_barrier();
-        if (threadIdx.x == 0 && (split || net == 0) && q.ld_part != nullptr) {   // (the inverse has none)
+        if (threadIdx.x == 0 && (split || net == 0) && q.ld_part != nullptr) {   // (null: the plain inverse)
             double t = 0.0;
             for (int i = 0; i < NW; i++) t += lsl[i];
             double* dst = q.ld_part + (size_t)img * q.np;

@@ -435,7 +435,8 @@ struct CouplingOpts {
     // written by this layer's k_net_lds from nz->src (the fused gather)
     const InputPrepArgs* nz = nullptr;
 };
-// One coupling layer: u -> v. dir=+1 forward (ld_part may collect the sum of s), dir=-1 inverse.
+// One coupling layer: u -> v. dir=+1 forward, dir=-1 inverse; ld_part (may be null) collects the layer's
+// per-image sum of s in either direction, written by whichever kernel applies the law.
 void run_coupling(Exec& E, const Coupling& c, const float* u, float* v, double* ld_part, int dir,
                   const CouplingOpts& o = CouplingOpts{});
 

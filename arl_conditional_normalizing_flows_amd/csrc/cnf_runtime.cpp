@@ -212,7 +212,7 @@ static void check_launch() { hip_check(hipGetLastError(), "kernel launch"); }
 
 using namespace cnf;
 
-// host-only dry run of the B-image forward (direction +1) or inverse (-1) schedule: nothing is launched or
+// host-only dry run of the B-image forward (direction +1), inverse (-1) or inverse-with-log-det (-2) schedule: nothing is launched or
 // dereferenced, the launch names land in p.dry_launches; throws what the real call would throw before its
 // first launch (defined after the schedules, below)
 static void dry_run(Plan& p, int B, int direction);
@@ -630,8 +630,11 @@ int cnf_adam_step(float* params, const float* grads, float* m, float* v, int64_t
 }
 
 // append: keep the launches recorded so far (cnf_flow_sample records one inverse per chunk)
+// logdet_per_image (may be null): every coupling's law also writes its log-det partial slots, reduced per
+// image into -(sum of s); ld_slots: the slots are written and left to the caller (cnf_flow_sample_logp)
 static void flow_inverse(Plan& p, const float* params, const float* aux, const float* zy, float* xy, void* workspace,
-                         int B, hipStream_t stream, bool append = false);
+                         int B, hipStream_t stream, bool append = false, float* logdet_per_image = nullptr,
+                         bool ld_slots = false);
 
 int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux, const float* zy, float* xy,
                      void* workspace, int B, void* stream) {
@@ -645,15 +648,30 @@ int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux, cons
     CNF_CATCH
 }
 
+int cnf_flow_inverse_logdet(cnf_plan* plan, const float* params, const float* aux, const float* zy, float* xy,
+                            float* logdet_per_image, void* workspace, int B, void* stream) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!plan || !params || !aux || !xy || !zy || !logdet_per_image || !workspace || B <= 0)
+        return fail(CNF_E_INVALID, "null argument or B <= 0");
+    if (xy == zy) return fail(CNF_E_INVALID, "zy and xy must not alias (out-of-place only)");
+    CNF_TRY
+    flow_inverse(*plan->p, params, aux, zy, xy, workspace, B, (hipStream_t)stream, false, logdet_per_image);
+    return CNF_OK;
+    CNF_CATCH
+}
+
 }  // extern "C"
 
 // cFlow.call(zy, -1) (:1774-1798) as a launch schedule
 static void flow_inverse(Plan& p, const float* params, const float* aux, const float* zy, float* xy, void* workspace,
-                         int B, hipStream_t stream, bool append) {
+                         int B, hipStream_t stream, bool append, float* logdet_per_image, bool ld_slots) {
     if (!p.dry) ensure_tables(p);
     if (!append) p.recorded.clear();
     Exec E{p, params, aux, (char*)workspace, p.layout(B), B, stream};
     const WsLayout& L = E.L;
+    // log-det slots [couplings][B][ld_parts], as the forward's: each coupling's block is written once, by
+    // the kernel that applies its law (k_coupling, the next k_net_lds, or the boundary k_map2)
+    double* ld = logdet_per_image != nullptr || ld_slots ? E.at<double>(L.ld) : nullptr;
     float* buf[2] = {E.at<float>(L.uv[0]), E.at<float>(L.uv[1])};
     const int nuv = (int)L.n_uv;
     const int* T = p.dtab(0);
@@ -687,7 +705,7 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
             o.pend = have_pend ? &pend : nullptr;
             o.defer = defers(p, c, li, -1);
             o.out_pend = &next;
-            run_coupling(E, c, cur, nxt, nullptr, -1, o);
+            run_coupling(E, c, cur, nxt, ld != nullptr ? ld + (size_t)c.index * B * L.ld_parts : nullptr, -1, o);
             pend = next;
             have_pend = o.defer;
             cur = nxt;
@@ -723,6 +741,11 @@ static void flow_inverse(Plan& p, const float* params, const float* aux, const f
         E.record("copy", 0, 2.0 * bytes, [=](void* st) {
             (void)hipMemcpyAsync(xy, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st);
         });
+    }
+    if (logdet_per_image != nullptr) {   // log|det d xy / d zy| = -(sum of s), the fixed-order fp64 reduction
+        const int nl = (int)p.couplings.size(), np = L.ld_parts;
+        E.record("k_ld_reduce", 0, 8.0 * B * nl * np,
+                 [=](void* st) { launch_ld_reduce(ld, logdet_per_image, B, nl, np, 0, (hipStream_t)st, 1); });
     }
     if (!p.dry) check_launch();
 }
@@ -776,15 +799,18 @@ size_t cnf_plan_sample_workspace_bytes(const cnf_plan* plan, int B, const cnf_sa
     return sample_layout(*plan->p, B, desc->chunk).total;
 }
 
-int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const float* y,
-                    const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
-                    void* workspace, int B, void* stream) {
+// the body of cnf_flow_sample (log_prob null: its launches, exactly) and cnf_flow_sample_logp
+static int flow_sample(const char* who, cnf_plan* plan, const float* params, const float* aux, const float* y,
+                       const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                       float* log_prob, void* workspace, int B, void* stream) {
     OptScope os_(plan ? &plan->p->opts : nullptr);
-    if (!plan || !params || !aux || !workspace) return fail(CNF_E_INVALID, "cnf_flow_sample: null argument");
-    if (!y) return fail(CNF_E_INVALID, "cnf_flow_sample: null y");
-    if (const char* e = sample_desc_error(*plan->p, B, desc)) return fail(CNF_E_INVALID, std::string("cnf_flow_sample: ") + e);
-    if (!samples && !mean && !std && !y_dev)
-        return fail(CNF_E_INVALID, "cnf_flow_sample: no output requested (samples, mean, std, y_dev all null)");
+    const std::string w(who);
+    if (!plan || !params || !aux || !workspace) return fail(CNF_E_INVALID, w + ": null argument");
+    if (!y) return fail(CNF_E_INVALID, w + ": null y");
+    if (const char* e = sample_desc_error(*plan->p, B, desc)) return fail(CNF_E_INVALID, w + ": " + e);
+    if (!samples && !mean && !std && !y_dev && !log_prob)
+        return fail(CNF_E_INVALID, w + ": no output requested (samples, mean, std, y_dev" +
+                                       (w == "cnf_flow_sample" ? "" : ", log_prob") + " all null)");
     CNF_TRY
     Plan& p = *plan->p;
     const cnf_flow_desc& d = p.desc;
@@ -817,17 +843,38 @@ int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const
         Exec E{p, params, aux, ws, p.layout(n), n, (hipStream_t)stream};
         E.record("k_latent", 0, 4.0 * n * px * (2 * d.io_d - d.x_d),
                  [=](void* st) { launch_latent(c, y, zy, T, seed, off, (hipStream_t)st); });
-        flow_inverse(p, params, aux, zy, xy, ws, n, (hipStream_t)stream, true);
+        flow_inverse(p, params, aux, zy, xy, ws, n, (hipStream_t)stream, true, nullptr, log_prob != nullptr);
         if (samples != nullptr || stats)
             E.record("k_sample_fold", 0, 4.0 * n * px * d.x_d * (samples ? 2 : 1),
                      [=](void* st) { launch_sample_fold(c, fa, (hipStream_t)st); });
         if (y_dev != nullptr)
             E.record("k_sample_ydev", 0, 8.0 * n * px * (d.io_d - d.x_d),
                      [=](void* st) { launch_sample_ydev(c, xy, y, y_dev, (hipStream_t)st); });
+        if (log_prob != nullptr) {
+            // the slots the chunk's inverse just wrote, read here: no reduce launch per chunk
+            const double* ld = E.at<double>(E.L.ld);
+            const int nl = (int)p.couplings.size(), np = E.L.ld_parts;
+            E.record("k_sample_logp", 0, 4.0 * n * px * d.x_d + 8.0 * n * nl * np,
+                     [=](void* st) { launch_sample_logp(c, zy, ld, nl, np, log_prob, (hipStream_t)st); });
+        }
     }
     check_launch();
     return CNF_OK;
     CNF_CATCH
+}
+
+int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                    const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                    void* workspace, int B, void* stream) {
+    return flow_sample("cnf_flow_sample", plan, params, aux, y, desc, samples, mean, std, y_dev, nullptr, workspace, B,
+                       stream);
+}
+
+int cnf_flow_sample_logp(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                         const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                         float* log_prob, void* workspace, int B, void* stream) {
+    return flow_sample("cnf_flow_sample_logp", plan, params, aux, y, desc, samples, mean, std, y_dev, log_prob,
+                       workspace, B, stream);
 }
 
 }  // extern "C"
@@ -841,8 +888,8 @@ static void dry_run(Plan& p, int B, int direction) {
     try {
         if (direction > 0)
             flow_forward(p, f, f, f, g, g, fake, B, nullptr, false);
-        else
-            flow_inverse(p, f, f, f, g, fake, B, nullptr);
+        else   // (-2: with the log-det)
+            flow_inverse(p, f, f, f, g, fake, B, nullptr, false, direction == -2 ? g + (1 << 18) : nullptr);
     } catch (...) {
         p.dry = false;
         throw;
@@ -890,6 +937,30 @@ int cnf_coupling_inverse(cnf_plan* plan, int layer, const float* params, const f
     p.recorded.clear();
     Exec E{p, params, aux, (char*)workspace, p.layout(B), B, (hipStream_t)stream};
     run_coupling(E, p.couplings[p.layers[layer].ci], v, u, nullptr, -1);
+    check_launch();
+    return CNF_OK;
+    CNF_CATCH
+}
+
+int cnf_coupling_inverse_logdet(cnf_plan* plan, int layer, const float* params, const float* aux, const float* v,
+                                float* u, float* logdet_accum, void* workspace, int B, void* stream) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!plan || !params || !aux || !u || !v || !workspace || B <= 0) return fail(CNF_E_INVALID, "null argument");
+    CNF_TRY
+    Plan& p = *plan->p;
+    if (layer < 0 || layer >= (int)p.layers.size() || p.layers[layer].kind != CNF_LAYER_COUPLING)
+        return fail(CNF_E_INVALID, "layer is not a coupling layer");
+    if (u == v) return fail(CNF_E_INVALID, "u and v must not alias");
+    ensure_tables(p);
+    p.recorded.clear();
+    Exec E{p, params, aux, (char*)workspace, p.layout(B), B, (hipStream_t)stream};
+    double* ld = E.at<double>(E.L.ld);
+    run_coupling(E, p.couplings[p.layers[layer].ci], v, u, logdet_accum ? ld : nullptr, -1);
+    if (logdet_accum) {   // -= the per-image sum of s
+        const int np = E.L.ld_parts;
+        E.record("k_ld_reduce", 0, 0,
+                 [=](void* st) { launch_ld_reduce(ld, logdet_accum, B, 1, np, 1, (hipStream_t)st, 1); });
+    }
     check_launch();
     return CNF_OK;
     CNF_CATCH
@@ -1256,11 +1327,12 @@ int cnf_debug_gc_launch_shapes(cnf_plan* plan, int B, int* words, int cap) {
     return (int)g.size() * GCSHAPE_WORDS;
 }
 
-// launch names of a B-image forward (direction +1) or inverse (-1) from a host-only dry run, one per
+// launch names of a B-image forward (direction +1), inverse (-1) or inverse with log-det (-2:
+// cnf_flow_inverse_logdet) from a host-only dry run, one per
 // line into out (cap bytes, NUL-terminated); returns the number of launches, -1 on error
 int cnf_debug_schedule(cnf_plan* plan, int B, int direction, char* out, int cap) {
     OptScope os_(plan ? &plan->p->opts : nullptr);
-    if (!plan || !out || cap <= 0 || B <= 0 || (direction != 1 && direction != -1)) return -1;
+    if (!plan || !out || cap <= 0 || B <= 0 || (direction != 1 && direction != -1 && direction != -2)) return -1;
     Plan& p = *plan->p;
     CNF_TRY
     dry_run(p, B, direction);

@@ -4,6 +4,7 @@
 //   k_latent       one chunk of zy: temperature * N(0,1) on the x channels, y[b] on the rest
 //   k_sample_fold  one pass over a chunk's xy_hat: post-transform, samples, running (K, S1, S2), mean / std
 //   k_sample_ydev  per image sum |y_hat - y|
+//   k_sample_logp  per image log-density of the draw: the prior's log N(z; 0, I) plus the inverse's log-det slots
 // All HBM-bound element / reduction kernels; no atomics, every sum in a fixed order.
 #include <hip/hip_runtime.h>
 
@@ -138,6 +139,29 @@ __global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, const float*
     if (lane == 0) y_dev[g] = (float)s;
 }
 
+// one wave per image of the chunk: log_prob[g] = log N(z; 0, I) + sum over couplings of sum s, from the
+// chunk's latent (the x channels of zy as stored) and the log-det partial slots part[nl][n][np] the
+// chunk's inverse left in its workspace. q = sum z^2: fp64 lane sums over the image's HW * x_d latent
+// elements in element order, then the wave sum; L: the slots in k_ld_reduce's order (ld_slot_sum).
+__global__ __launch_bounds__(256) void k_sample_logp(SampleChunk q, const float* __restrict__ zy,
+                                                     const double* __restrict__ part, int nl, int np,
+                                                     float* __restrict__ log_prob) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= q.n) return;   // (whole waves)
+    const int n = q.HW * q.x_d;
+    const float* __restrict__ zi = zy + (size_t)i * q.HW * q.D;
+    double s = 0.0;
+    for (int e = lane; e < n; e += 64) {
+        const int p = e / q.x_d, c = e - p * q.x_d;
+        const double z = (double)zi[(size_t)p * q.D + c];
+        s += z * z;
+    }
+    s = wave_sum(s);
+    const double L = ld_slot_sum(part, q.n, i, nl, np, lane);
+    if (lane == 0) log_prob[q.g0 + i] = (float)(-0.5 * s - 0.5 * (double)n * LOG_2PI_D + L);
+}
+
 int grid_for(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
@@ -167,6 +191,11 @@ void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream
 
 void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st) {
     CNF_LAUNCH(k_sample_ydev, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, y, y_dev);
+}
+
+void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
+                        hipStream_t st) {
+    CNF_LAUNCH(k_sample_logp, dim3((c.n + 3) / 4), dim3(256), 0, st, c, zy, ld_part, nl, np, log_prob);
 }
 
 }  // namespace cnf

@@ -227,6 +227,19 @@ class coupling_layer(Layer):
                                                ptr(ws), B, _stream()), 'cnf_coupling_inverse')
         return u, zy
 
+    def backward_and_Jacobian(self, v, sum_log_det_J, zy):
+        """backward that also accumulates this layer's log|det du/dv| = -(per-image sum of s) into
+        sum_log_det_J: the mirror of forward_and_Jacobian (cnf_coupling_inverse_logdet)."""
+        v = self._check(v, 'v')
+        f = self._flow
+        B = v.shape[0]
+        u = torch.empty_like(v)
+        ld = torch.zeros(B, device=v.device, dtype=torch.float32)
+        ws = f._workspace(B)
+        check(_lib.load().cnf_coupling_inverse_logdet(f._plan, self._layer, ptr(f.params), ptr(f._aux), ptr(v), ptr(u),
+                                                      ptr(ld), ptr(ws), B, _stream()), 'cnf_coupling_inverse_logdet')
+        return u, _accumulate_logdet(sum_log_det_J, ld), zy
+
     def gradients(self, u, dv, dlogdet=0.0):
         """Vector-Jacobian product of forward_and_Jacobian at u: (dL/du, dL/dparams) for
         dL/dv = dv and dL/d(per-image log-det) = dlogdet (the training backward of this layer;
@@ -449,9 +462,11 @@ class cFlow:
         return [self.loss_tracker, self.z_loss_tracker, self.y_loss_tracker, self.detJ_loss_tracker]
 
     # -- the hot path ---------------------------------------------------------------------------
-    def call(self, uv, direction=-1, per_image_logdet=False, layerwise=False, noise=None):
+    def call(self, uv, direction=-1, per_image_logdet=False, layerwise=False, noise=None, inverse_logdet=False):
         """cFlow.call (:1723-1798). direction=+1: xy -> (zy, log_detJ) with log_detJ the batch-mean
-        scalar (a (B,) tensor with per_image_logdet=True); direction=-1: zy -> xy.
+        scalar (a (B,) tensor with per_image_logdet=True); direction=-1: zy -> xy, or with
+        inverse_logdet=True (xy, logdet) with logdet[B] = log|det d xy / d zy| per image, minus the sum of
+        every coupling layer's s (cnf_flow_inverse_logdet; xy is the plain inverse's bit for bit).
         layerwise=True walks layers_list through the per-layer entry points exactly as the
         reference loop does; the default runs the whole schedule in one native call.
         noise=(alpha, seed, offset[, logit_a]) (direction=+1): the input prepared as the reference's
@@ -466,6 +481,8 @@ class cFlow:
         if tuple(uv.shape[1:]) != tuple(self.io_shape):
             raise ValueError(f'input shape {tuple(uv.shape)} != [None, {self.io_shape}]')
         B = uv.shape[0]
+        if inverse_logdet and direction != -1:
+            raise ValueError('inverse_logdet applies to direction=-1 only (direction=+1 returns its log-det already)')
         if noise is not None:
             if direction != 1:
                 raise ValueError('noise applies to the forward direction only')
@@ -500,9 +517,14 @@ class cFlow:
             return zy, (ld if per_image_logdet else ld.mean())
         elif direction == -1:
             if layerwise:
-                return self._call_layerwise_inverse(uv)
+                return self._call_layerwise_inverse(uv, inverse_logdet)
             xy = torch.empty_like(uv)
             ws = self._workspace(B)
+            if inverse_logdet:
+                ld = torch.empty(B, device=uv.device, dtype=torch.float32)
+                check(_lib.load().cnf_flow_inverse_logdet(self._plan, ptr(self.params), ptr(self._aux), ptr(uv), ptr(xy),
+                                                          ptr(ld), ptr(ws), B, _stream()), 'cnf_flow_inverse_logdet')
+                return xy, ld
             check(_lib.load().cnf_flow_inverse(self._plan, ptr(self.params), ptr(self._aux), ptr(uv), ptr(xy),
                                                ptr(ws), B, _stream()), 'cnf_flow_inverse')
             return xy
@@ -524,19 +546,28 @@ class cFlow:
             vu, zy = layer.backward(vu, zy)
         return vu, log_detJ
 
-    def _call_layerwise_inverse(self, uv):
+    def _call_layerwise_inverse(self, uv, inverse_logdet=False):
+        B = uv.shape[0]
         zy = None
         if self.squeeze_factor_layers_list:                     # :1782-1788
             for layer in self.squeeze_factor_layers_list:
                 uv, _, zy = layer.forward_and_Jacobian(uv, None, zy)
         vu = uv
+        if inverse_logdet:   # the couplings through backward_and_Jacobian; squeeze / factor layers have none
+            ld = torch.zeros(B, device=uv.device, dtype=torch.float32)
+            for layer in reversed(self.layers_list):
+                if isinstance(layer, coupling_layer):
+                    vu, ld, zy = layer.backward_and_Jacobian(vu, ld, zy)
+                else:
+                    vu, zy = layer.backward(vu, zy)
+            return vu, ld
         for layer in reversed(self.layers_list):                # :1793-1796
             vu, zy = layer.backward(vu, zy)
         return vu
 
     # -- sampling -------------------------------------------------------------------------------
     def sample(self, y, num_samples, temperature=1.0, seed=0, offset=0, chunk=None, logit_a=None, residual=False,
-               return_samples=True, return_stats=True, return_y_dev=False):
+               return_samples=True, return_stats=True, return_y_dev=False, return_log_prob=False):
         """num_samples draws of x given each condition y and their per-pixel statistics: the recipe of
         TOYcINN.py:807-817 (z from the prior, concat y, the model in the generative direction, :1774-1798)
         with the post-transforms and the reduction over the draws, in one native call (cnf_flow_sample).
@@ -549,7 +580,11 @@ class cFlow:
 
         Returns a dict with the requested ones of 'samples' [B,S,H,W,x_d], 'mean' and 'std' [B,H,W,x_d]
         (over the draws, population form: np.std) and 'y_dev' [B,S] (sum |y_hat - y| of each draw: how
-        well it honours its condition). With return_samples=False no [B,S,...] tensor is allocated."""
+        well it honours its condition). With return_samples=False no [B,S,...] tensor is allocated.
+        return_log_prob=True adds 'log_prob' [B,S]: the model's log-density of each draw in the flow's input
+        space (before de_logitify / residual), llz + the sum of every coupling's s, i.e. what nll_sums reports
+        as llz + logdet for that draw's (xy_hat, zy) -- from the inverse's own s (cnf_flow_sample_logp), for
+        ranking the draws of a condition, importance weights or typicality checks. It may be the only output."""
         y = _as_input(y, 'y')
         H, W, D = self.io_shape
         if y.dim() == 3:
@@ -579,6 +614,13 @@ class cFlow:
             out['mean'], out['std'] = new(B, H, W, self.x_d), new(B, H, W, self.x_d)
         if return_y_dev:
             out['y_dev'] = new(B, max(S, 0))
+        if return_log_prob:
+            out['log_prob'] = new(B, max(S, 0))
+            check(lib.cnf_flow_sample_logp(self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc),
+                                           ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')),
+                                           ptr(out.get('y_dev')), ptr(out['log_prob']), ptr(ws), B, _stream()),
+                  'cnf_flow_sample_logp')
+            return out
         check(lib.cnf_flow_sample(self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc),
                                   ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')),
                                   ptr(out.get('y_dev')), ptr(ws), B, _stream()),

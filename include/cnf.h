@@ -164,6 +164,18 @@ int cnf_flow_forward_noise(cnf_plan* plan, const float* params, const float* aux
 int cnf_flow_inverse(cnf_plan* plan, const float* params, const float* aux,
                      const float* zy, float* xy, void* workspace, int B, void* stream);
 
+/* cnf_flow_inverse that also returns logdet_per_image[B] = log|det d xy / d zy|
+ * = -(sum over coupling layers of sum_{h,w,c} s), s = tanh_w * tanh(s_pre) as the inverse itself
+ * evaluates it (from the conditioning half it sees). xy is bit for bit cnf_flow_inverse's.
+ * Every coupling's sum goes into its log-det partial slots of the workspace (the forward's slots:
+ * cnf_plan_workspace_bytes is unchanged), written once by the kernel that applies its law, and one
+ * fixed-order fp64 reduction per image follows (no atomics: the result does not depend on B, the
+ * stream or the workspace's earlier contents). Aliasing rules and argument errors as
+ * cnf_flow_inverse; a NULL logdet_per_image is CNF_E_INVALID before any HIP call. */
+int cnf_flow_inverse_logdet(cnf_plan* plan, const float* params, const float* aux,
+                            const float* zy, float* xy, float* logdet_per_image,
+                            void* workspace, int B, void* stream);
+
 /* Conditional sampling: S draws of x given y for each of B conditions, and their per-pixel
  * statistics. Replaces the recipe the reference's users write by hand (TOYcINN.py:807-817: draw z
  * from the prior, concatenate the condition y, call the model in the generative direction,
@@ -207,6 +219,21 @@ int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const
                     const cnf_sample_desc* desc, float* samples, float* mean, float* std,
                     float* y_dev, void* workspace, int B, void* stream);
 
+/* cnf_flow_sample plus log_prob[B][S] (may be NULL; counts as a requested output):
+ * log_prob[b,s] = llz + sum_layers sum s, i.e. the llz + logdet that cnf_nll reports for the pair
+ * (xy_hat, zy) of that draw: the model's log-density of the draw in the flow's input space (before
+ * de_logitify / residual; the prior is N(0, I) whatever the temperature; y_dev carries the lly part).
+ * Arithmetic, with z the fp32 latent as stored in the chunk's zy and n = H*W*x_d: q = the fp64 sum
+ * of (double)z * (double)z over the image's latent (lane-strided partial sums in element order, then
+ * a fixed-order wave sum), L = the fp64 sum of the image's log-det partial slots over all couplings
+ * in cnf_flow_inverse_logdet's reduction order, log_prob = (float)(-0.5*q - 0.5*n*log(2*pi) + L).
+ * One extra launch per chunk, which reads the slots directly. cnf_sample_desc, the workspace size
+ * (cnf_plan_sample_workspace_bytes) and the bits of samples, mean, std and y_dev are
+ * cnf_flow_sample's; no result depends on chunk, bit for bit. */
+int cnf_flow_sample_logp(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                         const cnf_sample_desc* desc, float* samples, float* mean, float* std,
+                         float* y_dev, float* log_prob, void* workspace, int B, void* stream);
+
 /* coupling_layer.forward_and_Jacobian (:1258-1328) for layer `layer` of
  * layers_list: u -> v (shape of the layer's in_shape); logdet_accum[B] +=
  * per-image sum of A(u1) (pass NULL to skip). u and v must not alias. */
@@ -217,6 +244,12 @@ int cnf_coupling_forward(cnf_plan* plan, int layer, const float* params, const f
 /* coupling_layer.backward (:1333-1394): v -> u. */
 int cnf_coupling_inverse(cnf_plan* plan, int layer, const float* params, const float* aux,
                          const float* v, float* u, void* workspace, int B, void* stream);
+
+/* cnf_coupling_inverse with logdet_accum[B] -= per-image sum of s (NULL: skip), the mirror of
+ * cnf_coupling_forward's logdet_accum. */
+int cnf_coupling_inverse_logdet(cnf_plan* plan, int layer, const float* params, const float* aux,
+                                const float* v, float* u, float* logdet_accum,
+                                void* workspace, int B, void* stream);
 
 /* squeeze_layer (:155-217): dir=+1 space_to_depth(2) in TF channel order,
  * dir=-1 depth_to_space(2). in: [B,H,W,C] (dir=+1) or [B,H,W,4C'] (dir=-1). */
