@@ -17,11 +17,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/cnf.h"
-
-namespace cnf {
-int set_error(int code, const char* msg);
-}
+#include "cnf_api.h"
 
 struct cnf_comm {
     ncclComm_t comm = nullptr;

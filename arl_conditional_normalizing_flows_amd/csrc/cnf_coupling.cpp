@@ -9,14 +9,11 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "cnf_api.h"
 #include "cnf_kernels.h"
 #include "cnf_plan.h"
 
 namespace cnf {
-
-namespace {
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-}  // namespace
 
 // ----------------------------------------------------------------------------------------------
 // geometry

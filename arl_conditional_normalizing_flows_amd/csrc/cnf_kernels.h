@@ -18,7 +18,7 @@ constexpr double LOG_2PI_D = 1.8378770664093453;
 // S2 = sum((x - K)^2) over its n values of LeakyReLU(out), K a sample of them (fp32, 16 bytes)
 constexpr int LNP = 4;
 // LN partial slots per image a consumer wave folds from its prologue loads, per lane (cnf_device.h
-// in_ln_fetch); producers of more than 64 * LN_FETCH slots get a k_ln_merge launch (cnf_runtime.cpp)
+// in_ln_fetch); producers of more than 64 * LN_FETCH slots get a k_ln_merge launch (cnf_coupling.cpp)
 constexpr int LN_FETCH = 8;
 
 constexpr int MAXPROB = 12;
@@ -371,17 +371,28 @@ int read_gc_stamps(long long* host, int n);
 int gc_num_shapes();   // shape-specialised k_gc instantiations compiled in
 // k_toy (cnf_toy.hip): TOYcINN dense flow, one thread per 3-dimensional sample
 constexpr int TOY_MAXL = 128;
+// the toy flow as its three kernels read it: nl coupling networks of hidden width H and L hidden Dense
+// layers over (x_d, 3 - x_d) points, run in the order `order`
+struct ToyNet {
+    int nl, H, L, x_d;
+    int order[TOY_MAXL];        // mask_indices
+    int net_off[TOY_MAXL + 1];  // float offset of network j's parameters; [nl]: the parameter count
+};
+// inputs of the nets of coupling network j (its mask's u1; they write the other 3 - n1 components). The
+// device side of the rule: toy_mask, cnf_toy_device.h
+constexpr int toy_n1(int j) { return (j % 6) < 3 ? 1 : 2; }
+// workgroups over n samples (draws) in tiles of ts
+constexpr int64_t toy_tiles(int64_t n, int ts) { return (n + ts - 1) / ts; }
 struct ToyArgs {
     const float* params;   // canonical flat parameters (per network j: b-block then A-block)
     const float* u;        // [B][3]
     float* v;              // [B][3]
     float* log_detJ;       // [B] (direction -1) or null
     float* per_sample;     // [B][3] (llz, lly, log_detJ) of log_loss (direction -1) or null
-    int B, nl, H, L, x_d, dir;
+    int B, dir;
     float lambda_y;
-    int order[TOY_MAXL];        // mask_indices
-    int net_off[TOY_MAXL + 1];  // float offset of network j's parameters
-    float* save_u;              // [nl][B][3] input of every executed coupling layer, by step (training) or null
+    ToyNet flow;
+    float* save_u;         // [nl][B][3] input of every executed coupling layer, by step (training) or null
 };
 void launch_toy(const ToyArgs& a, int lds_floats, hipStream_t st);
 // k_toy_bwd / k_toy_grad_sum (cnf_toy_train.hip): backward of the whole toy flow, one workgroup per
@@ -396,10 +407,9 @@ struct ToyBwdArgs {
     const float* zy;       // [B][3]
     const float* saved_u;  // [nl][B][3], as ToyArgs::save_u wrote it
     float* part;           // [tiles][num_params]
-    int B, nl, H, L, x_d, HP, num_params;
+    int B, HP, num_params;
     float lambda_y, inv_batch;
-    int order[TOY_MAXL];
-    int net_off[TOY_MAXL + 1];
+    ToyNet flow;
 };
 int toy_bwd_hp(int H);                   // LDS row stride of one sample's hidden vector
 size_t toy_bwd_lds_bytes(int H, int L);  // dynamic LDS of k_toy_bwd
@@ -418,13 +428,12 @@ struct ToySampleArgs {
     float* y_dev;          // [B][S] or null
     unsigned* hist;        // [B][G] / [B][G][G] or null
     float* part;           // [B][tiles][x_d][TOY_SAMPLE_PART]
-    int B, S, tiles, nl, H, L, x_d, HP;
+    int B, S, tiles, HP;
     float temperature;
     unsigned long long seed, offset;
     int G;                 // histogram bins per component
     float lo[2], scale[2];
-    int order[TOY_MAXL];
-    int net_off[TOY_MAXL + 1];
+    ToyNet flow;
 };
 size_t toy_sample_lds_bytes(int H);   // dynamic LDS of k_toy_sample
 void launch_toy_sample(const ToySampleArgs& a, hipStream_t st);

@@ -284,6 +284,12 @@ struct StreamActs {
 };
 
 struct Plan {
+    Plan() = default;
+    // frees what the members below hold on a device: the tables, events and streams (cnf_runtime.cpp); a
+    // plan that never touched one frees nothing
+    ~Plan();
+    Plan(const Plan&) = delete;
+    Plan& operator=(const Plan&) = delete;
     cnf_flow_desc desc{};
     std::vector<int> sfbl, rbl, nkl, cl;
     std::vector<Layer> layers;
@@ -375,6 +381,35 @@ void coupling_layer_backward(Plan& p, int ci, const float* params, const float* 
 // builds the plan; throws std::invalid_argument with the reference's assertion text
 Plan* build_plan(const cnf_flow_desc* d);
 
+// cnf_runtime.cpp
+// uploads the plan's index tables to the current device on its first call there (not capturable)
+void ensure_tables(Plan& p);
+
+// cnf_schedule.cpp
+// the forward schedule; save_inputs: also copy every coupling layer's input into the training
+// workspace (cnf_flow_forward_train)
+// nz (cnf_flow_forward_noise): xy is the caller's buffer for the noisy input, which the first coupling's
+// k_net_lds writes while gathering from nz->src with the noise applied (a k_noise pass into it first when
+// that layer is streamed)
+void flow_forward(Plan& p, const float* params, const float* aux, const float* xy, float* zy,
+                  float* logdet_per_image, void* workspace, int B, hipStream_t stream, bool save_inputs,
+                  const InputPrepArgs* nz = nullptr);
+struct InverseOpts {
+    // keep the launches recorded so far (cnf_flow_sample records one inverse per chunk)
+    bool append = false;
+    // every coupling's law also writes its log-det partial slots, reduced per image into -(sum of s)
+    float* logdet_per_image = nullptr;
+    // the slots are written and left to the caller (cnf_flow_sample_logp)
+    bool ld_slots = false;
+};
+// cFlow.call(zy, -1) (:1774-1798) as a launch schedule
+void flow_inverse(Plan& p, const float* params, const float* aux, const float* zy, float* xy, void* workspace, int B,
+                  hipStream_t stream, const InverseOpts& o = InverseOpts{});
+// host-only dry run of the B-image forward (direction +1), inverse (-1) or inverse-with-log-det (-2) schedule:
+// nothing is launched or dereferenced, the launch names land in p.dry_launches; throws what the real call
+// would throw before its first launch
+void dry_run(Plan& p, int B, int direction);
+
 // ---- cnf_coupling.cpp: one coupling layer as launches -------------------------------------------------
 // row-band tiling of the 3x3 kernels: TH rows per tile, tiles per image, 64 * MR pixels per tile;
 // throws std::invalid_argument for an image wider than a tile
@@ -441,3 +476,8 @@ void run_coupling(Exec& E, const Coupling& c, const float* u, float* v, double* 
                   const CouplingOpts& o = CouplingOpts{});
 
 }  // namespace cnf
+
+// the C ABI's opaque plan handle (include/cnf.h)
+struct cnf_plan {
+    cnf::Plan* p;
+};

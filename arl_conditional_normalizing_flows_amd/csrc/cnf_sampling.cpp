@@ -1,0 +1,146 @@
+// cnf_sampling.cpp — conditional sampling (include/cnf.h cnf_flow_sample; kernels: cnf_sample.hip): latents
+// per chunk, the inverse schedule (cnf_schedule.cpp) and the folds of the draws into the outputs.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "cnf_api.h"
+#include "cnf_plan.h"
+
+using namespace cnf;
+
+namespace {
+
+// the sample workspace: the inverse workspace of `chunk` images, one chunk of zy and of xy_hat, and the
+// statistics state (K, S1, S2) [3][B][H][W][x_d]
+struct SampleLayout {
+    size_t zy = 0, xy = 0, state = 0, total = 0;
+};
+SampleLayout sample_layout(const Plan& p, int B, int chunk) {
+    const cnf_flow_desc& d = p.desc;
+    const size_t n_uv = (size_t)d.io_h * d.io_w * d.io_d;
+    SampleLayout L;
+    size_t off = align_up(p.layout(chunk).total, 256);
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    L.zy = take((size_t)chunk * n_uv * 4);
+    L.xy = take((size_t)chunk * n_uv * 4);
+    L.state = take((size_t)3 * B * d.io_h * d.io_w * d.x_d * 4);
+    L.total = off;
+    return L;
+}
+
+// the argument errors of cnf_flow_sample that need no pointer but the descriptor (null: fine)
+const char* sample_desc_error(const Plan& p, int B, const cnf_sample_desc* s) {
+    if (s == nullptr) return "null sample descriptor";
+    if (B < 1) return "B must be >= 1";
+    if (s->num_samples < 1) return "num_samples must be >= 1";
+    if (s->chunk < 1) return "chunk must be >= 1";
+    if (!(s->temperature >= 0.f) || std::isinf(s->temperature)) return "temperature must be finite and >= 0";
+    if (s->logit_a != 0.f && !(s->logit_a > 0.f && s->logit_a < 0.5f))
+        return "logit_a must be 0 (no de_logitify) or in (0, 0.5)";
+    if (s->residual != 0 && p.desc.io_d - p.desc.x_d != p.desc.x_d)
+        return "residual needs y of x's depth (io_d - x_d == x_d)";
+    return nullptr;
+}
+
+// the body of cnf_flow_sample (log_prob null: its launches, exactly) and cnf_flow_sample_logp
+int flow_sample(const char* who, cnf_plan* plan, const float* params, const float* aux, const float* y,
+                const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev, float* log_prob,
+                void* workspace, int B, void* stream) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    const std::string w(who);
+    if (!plan || !params || !aux || !workspace) return fail(CNF_E_INVALID, w + ": null argument");
+    if (!y) return fail(CNF_E_INVALID, w + ": null y");
+    if (const char* e = sample_desc_error(*plan->p, B, desc)) return fail(CNF_E_INVALID, w + ": " + e);
+    if (!samples && !mean && !std && !y_dev && !log_prob)
+        return fail(CNF_E_INVALID, w + ": no output requested (samples, mean, std, y_dev" +
+                                       (w == "cnf_flow_sample" ? "" : ", log_prob") + " all null)");
+    CNF_TRY
+    Plan& p = *plan->p;
+    const cnf_flow_desc& d = p.desc;
+    ensure_tables(p);
+    p.recorded.clear();
+    const SampleLayout SL = sample_layout(p, B, desc->chunk);
+    char* ws = (char*)workspace;
+    float* zy = reinterpret_cast<float*>(ws + SL.zy);
+    float* xy = reinterpret_cast<float*>(ws + SL.xy);
+    const bool stats = mean != nullptr || std != nullptr;
+    SampleFoldArgs fa;
+    std::memset(&fa, 0, sizeof(fa));
+    fa.xy_hat = xy;
+    fa.y = y;
+    fa.samples = samples;
+    fa.state = stats ? reinterpret_cast<float*>(ws + SL.state) : nullptr;
+    fa.mean = mean;
+    fa.std = std;
+    fa.B = B;
+    fa.logit = desc->logit_a != 0.f ? 1 : 0;
+    fa.residual = desc->residual != 0 ? 1 : 0;
+    if (fa.logit) fa.lk = logit_consts(desc->logit_a);
+    const float T = desc->temperature;
+    const unsigned long long seed = desc->seed, off = desc->offset;
+    const long long total = (long long)B * desc->num_samples;
+    const double px = (double)d.io_h * d.io_w;
+    InverseOpts io;
+    io.append = true;                   // one recording for the whole call
+    io.ld_slots = log_prob != nullptr;  // k_sample_logp reads the slots: no reduce launch per chunk
+    for (long long g0 = 0; g0 < total; g0 += desc->chunk) {
+        const int n = (int)std::min<long long>(desc->chunk, total - g0);
+        const SampleChunk c{g0, n, desc->num_samples, d.io_h * d.io_w, d.io_d, d.x_d};
+        Exec E{p, params, aux, ws, p.layout(n), n, (hipStream_t)stream};
+        E.record("k_latent", 0, 4.0 * n * px * (2 * d.io_d - d.x_d),
+                 [=](void* st) { launch_latent(c, y, zy, T, seed, off, (hipStream_t)st); });
+        flow_inverse(p, params, aux, zy, xy, ws, n, (hipStream_t)stream, io);
+        if (samples != nullptr || stats)
+            E.record("k_sample_fold", 0, 4.0 * n * px * d.x_d * (samples ? 2 : 1),
+                     [=](void* st) { launch_sample_fold(c, fa, (hipStream_t)st); });
+        if (y_dev != nullptr)
+            E.record("k_sample_ydev", 0, 8.0 * n * px * (d.io_d - d.x_d),
+                     [=](void* st) { launch_sample_ydev(c, xy, y, y_dev, (hipStream_t)st); });
+        if (log_prob != nullptr) {
+            // the slots the chunk's inverse just wrote
+            const double* ld = E.at<double>(E.L.ld);
+            const int nl = (int)p.couplings.size(), np = E.L.ld_parts;
+            E.record("k_sample_logp", 0, 4.0 * n * px * d.x_d + 8.0 * n * nl * np,
+                     [=](void* st) { launch_sample_logp(c, zy, ld, nl, np, log_prob, (hipStream_t)st); });
+        }
+    }
+    check_launch();
+    return CNF_OK;
+    CNF_CATCH
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cnf_plan_sample_workspace_bytes(const cnf_plan* plan, int B, const cnf_sample_desc* desc) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!plan) return 0;
+    if (const char* e = sample_desc_error(*plan->p, B, desc)) {   // (the message for cnf_last_error)
+        (void)fail(CNF_E_INVALID, std::string("cnf_plan_sample_workspace_bytes: ") + e);
+        return 0;
+    }
+    return sample_layout(*plan->p, B, desc->chunk).total;
+}
+
+int cnf_flow_sample(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                    const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                    void* workspace, int B, void* stream) {
+    return flow_sample("cnf_flow_sample", plan, params, aux, y, desc, samples, mean, std, y_dev, nullptr, workspace, B,
+                       stream);
+}
+
+int cnf_flow_sample_logp(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                         const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev,
+                         float* log_prob, void* workspace, int B, void* stream) {
+    return flow_sample("cnf_flow_sample_logp", plan, params, aux, y, desc, samples, mean, std, y_dev, log_prob,
+                       workspace, B, stream);
+}
+
+}  // extern "C"

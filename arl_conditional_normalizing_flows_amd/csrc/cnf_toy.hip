@@ -13,12 +13,11 @@
 #include <cstdint>
 
 #include "cnf_kernels.h"
+#include "cnf_toy_device.h"
 
 namespace cnf {
 
 namespace {
-
-__device__ __forceinline__ float lrelu_t(float x) { return x >= 0.f ? x : LRELU_ALPHA * x; }
 
 // y[o] = sum_k x[k] W[k][o] + b[o] over LDS weights W [nin][nout] (row-major), b [nout];
 // compile-time bounds keep x / y in registers
@@ -47,12 +46,12 @@ __device__ __forceinline__ const float* toy_net(const float* p, const float* u1,
     dense<2, H>(u1, n1, p, p + n1 * Hr, Hr, h);
     p += n1 * Hr + Hr;
 #pragma unroll
-    for (int o = 0; o < H; o++) h[o] = lrelu_t(h[o]);
+    for (int o = 0; o < H; o++) h[o] = toy_lrelu(h[o]);
     for (int l = 0; l < L; l++) {
         dense<H, H>(h, Hr, p, p + Hr * Hr, Hr, t);
         p += Hr * Hr + Hr;
 #pragma unroll
-        for (int o = 0; o < H; o++) h[o] = lrelu_t(t[o]);
+        for (int o = 0; o < H; o++) h[o] = toy_lrelu(t[o]);
     }
     float y[2];
     dense<H, 2>(h, Hr, p, p + Hr * n2, n2, y);
@@ -72,38 +71,23 @@ __global__ __launch_bounds__(256) void k_toy(ToyArgs a) {
     if (valid)
         for (int c = 0; c < 3; c++) u[c] = a.u[(size_t)s * 3 + c];
     float ld = 0.f;
-    for (int step = 0; step < a.nl; step++) {
-        const int i = a.dir < 0 ? a.nl - 1 - step : step;   // direction -1: reverse index order (:300)
-        const int j = a.order[i];
-        const int t = j % 6;
-        // u1 / u2 index sets of mask type t (:149-163)
-        int i1[2], i2[2], n1, n2;
-        if (t < 3) {
-            n1 = 1;
-            n2 = 2;
-            i1[0] = t;
-            i1[1] = 0;
-            i2[0] = t == 0 ? 1 : 0;
-            i2[1] = t == 2 ? 1 : 2;
-        } else {
-            n1 = 2;
-            n2 = 1;
-            i1[0] = t == 5 ? 1 : 0;
-            i1[1] = t == 3 ? 1 : 2;
-            i2[0] = 5 - t;   // t=3 -> 2, t=4 -> 1, t=5 -> 0
-            i2[1] = 0;
-        }
+    for (int step = 0; step < a.flow.nl; step++) {
+        const int i = a.dir < 0 ? a.flow.nl - 1 - step : step;   // direction -1: reverse index order (:300)
+        const int j = a.flow.order[i];
+        const ToyMask m = toy_mask(j);   // u1 / u2 index sets (:149-163)
+        const int n1 = m.n1, n2 = m.n2;
+        const int i1[2] = {m.i1[0], m.i1[1]}, i2[2] = {m.i2[0], m.i2[1]};
         // stage both nets of coupling network j
-        const int n = a.net_off[j + 1] - a.net_off[j];
+        const int n = a.flow.net_off[j + 1] - a.flow.net_off[j];
         __syncthreads();
-        for (int e = threadIdx.x; e < n; e += 256) lw[e] = a.params[a.net_off[j] + e];
+        for (int e = threadIdx.x; e < n; e += 256) lw[e] = a.params[a.flow.net_off[j] + e];
         __syncthreads();
         if (a.save_u && valid)   // training forward: the activations the loss sees (k_toy_bwd reads them)
             for (int c = 0; c < 3; c++) a.save_u[((size_t)step * a.B + s) * 3 + c] = u[c];
         float u1[2] = {u[i1[0]], n1 > 1 ? u[i1[1]] : 0.f};
         float bv[2], av[2];
-        const float* p = toy_net<H>(lw, u1, n1, a.H, a.L, n2, bv);
-        toy_net<H>(p, u1, n1, a.H, a.L, n2, av);
+        const float* p = toy_net<H>(lw, u1, n1, a.flow.H, a.flow.L, n2, bv);
+        toy_net<H>(p, u1, n1, a.flow.H, a.flow.L, n2, av);
         for (int k = 0; k < n2; k++) {
             const float A = tanhf(av[k]);
             const float u2 = u[i2[k]];
@@ -120,9 +104,9 @@ __global__ __launch_bounds__(256) void k_toy(ToyArgs a) {
     if (a.dir < 0 && a.log_detJ) a.log_detJ[s] = ld;
     if (a.dir < 0 && a.per_sample) {
         // log_loss terms (:419-451): log N(z; 0, I_xd), -lambda_y |y - y'|_1, log_detJ
-        float llz = -0.5f * (float)a.x_d * (float)LOG_2PI_D, lly = 0.f;
+        float llz = -0.5f * (float)a.flow.x_d * (float)LOG_2PI_D, lly = 0.f;
         for (int c = 0; c < 3; c++) {
-            if (c < a.x_d)
+            if (c < a.flow.x_d)
                 llz -= 0.5f * u[c] * u[c];
             else
                 lly -= a.lambda_y * fabsf(u[c] - a.u[(size_t)s * 3 + c]);
@@ -137,11 +121,11 @@ void launch_toy(const ToyArgs& a, int lds_floats, hipStream_t st) {
     const dim3 g((a.B + 255) / 256), b(256);
     const size_t lds = (size_t)lds_floats * sizeof(float);
     // the hidden width is a compile-time register-array bound (the reference uses 32)
-    if (a.H == 32)
+    if (a.flow.H == 32)
         hipLaunchKernelGGL(k_toy<32>, g, b, lds, st, a);
-    else if (a.H <= 16)
+    else if (a.flow.H <= 16)
         hipLaunchKernelGGL(k_toy<16>, g, b, lds, st, a);
-    else if (a.H <= 32)
+    else if (a.flow.H <= 32)
         hipLaunchKernelGGL(k_toy<32>, g, b, lds, st, a);
     else
         hipLaunchKernelGGL(k_toy<64>, g, b, lds, st, a);

@@ -7,7 +7,7 @@
 //                       xy_hat in global memory. Coupling layers run in direction +1 (index order,
 //                       u2 = (v2 - b) / exp(tanh A), TOYcINN_make_model.py:370-375). Per layer and net the
 //                       hidden activations ping-pong between two [TS][HP] LDS images; the H x H Dense layers
-//                       run on v_mfma_f32_16x16x4_f32 (mma_tile, cnf_toy_mma.h; bias = the accumulator's
+//                       run on v_mfma_f32_16x16x4_f32 (mma_tile, cnf_toy_device.h; bias = the accumulator's
 //                       start, zero operands pad H to 16 / 4): a wave loads the B fragments of its 16-column
 //                       tile from global memory (L2-resident weights) into registers once per Dense layer and
 //                       reuses them over its row tiles, so per MFMA only the A element comes from LDS. The
@@ -24,7 +24,7 @@
 #include <cstdint>
 
 #include "cnf_device.h"
-#include "cnf_toy_mma.h"
+#include "cnf_toy_device.h"
 
 namespace cnf {
 
@@ -36,15 +36,13 @@ constexpr int NW = BT / 64;
 constexpr int RT = TS / 16;   // 16-row tiles of a draw tile
 static_assert(TS % 16 == 0 && TS <= BT, "one epilogue thread per draw");
 
-__device__ __forceinline__ float lrelu_s(float x) { return x >= 0.f ? x : LRELU_ALPHA * x; }
-
 }  // namespace
 
 // KS: k steps of the H x H MFMA layers (H <= 4 KS), the bound of the B-fragment register array
 template <int KS>
 __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int H = a.H, L = a.L, HP = a.HP;
+    const int H = a.flow.H, L = a.flow.L, HP = a.HP;
     float* act = sm;                   // [2][TS][HP] post-activation hidden vectors, ping-pong
     float* su = act + 2 * TS * HP;     // [TS][3] the draws' state: zy, then each layer's output, then xy_hat
     float* bo = su + 3 * TS;           // [TS][2] the b net's output
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
     const int s0 = tile * TS;
     const int cnt = a.S - s0 < TS ? a.S - s0 : TS;   // draws of this tile (>= 1); rows past them are zeros
     const int HT = (H + 15) / 16;
-    const int yd = 3 - a.x_d;
+    const int yd = 3 - a.flow.x_d;
     const float* __restrict__ yb = a.y + (size_t)b * yd;
     const int fd_s = tid / H, fd_o = tid - fd_s * H;   // the first Dense's element walk: start and step of (s, o)
     const int fd_ds = BT / H, fd_do = BT - fd_ds * H;
@@ -63,40 +61,26 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
         const int s = e / 3, c = e - 3 * s;
         float v = 0.f;
         if (s < cnt) {
-            if (c < a.x_d) {
-                const uint64_t g = (uint64_t)a.offset + ((uint64_t)b * (uint64_t)a.S + (uint64_t)(s0 + s)) * (uint64_t)a.x_d + c;
+            if (c < a.flow.x_d) {
+                const uint64_t g = (uint64_t)a.offset + ((uint64_t)b * (uint64_t)a.S + (uint64_t)(s0 + s)) * (uint64_t)a.flow.x_d + c;
                 v = a.temperature * instance_noise_value(0.f, false, 0.f, (uint64_t)a.seed, g);
             } else {
-                v = yb[c - a.x_d];
+                v = yb[c - a.flow.x_d];
             }
         }
         su[e] = v;
     }
 
-    for (int step = 0; step < a.nl; step++) {
-        const int j = a.order[step];
-        const int t = j % 6;
-        int i1[2], i2[2], n1, n2;   // u1 / u2 index sets of mask type t (:149-163), as k_toy
-        if (t < 3) {
-            n1 = 1;
-            n2 = 2;
-            i1[0] = t;
-            i1[1] = 0;
-            i2[0] = t == 0 ? 1 : 0;
-            i2[1] = t == 2 ? 1 : 2;
-        } else {
-            n1 = 2;
-            n2 = 1;
-            i1[0] = t == 5 ? 1 : 0;
-            i1[1] = t == 3 ? 1 : 2;
-            i2[0] = 5 - t;
-            i2[1] = 0;
-        }
-        const int net_floats = (a.net_off[j + 1] - a.net_off[j]) / 2;
+    for (int step = 0; step < a.flow.nl; step++) {
+        const int j = a.flow.order[step];
+        const ToyMask m = toy_mask(j);   // u1 / u2 index sets (:149-163), as k_toy
+        const int n1 = m.n1, n2 = m.n2;
+        const int i1[2] = {m.i1[0], m.i1[1]}, i2[2] = {m.i2[0], m.i2[1]};
+        const int net_floats = (a.flow.net_off[j + 1] - a.flow.net_off[j]) / 2;
         __syncthreads();   // su of the previous layer (or the latent) complete
 
         for (int net = 0; net < 2; net++) {   // b, then A
-            const float* __restrict__ p = a.params + a.net_off[j] + net * net_floats;
+            const float* __restrict__ p = a.params + a.flow.net_off[j] + net * net_floats;
             const int off_hid = n1 * H + H;
             const int off_last = off_hid + L * (H * H + H);
 
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
                 float y = p[n1 * H + o];
                 y = fmaf(su[3 * s + i1[0]], p[o], y);
                 if (n1 > 1) y = fmaf(su[3 * s + i1[1]], p[H + o], y);
-                act[s * HP + o] = lrelu_s(y);
+                act[s * HP + o] = toy_lrelu(y);
                 s += fd_ds;
                 o += fd_do;
                 if (o >= H) {
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
                             [&](int kk, int) { return bf[kk >> 2]; }, acc);
                         if (col < H) {
 #pragma unroll
-                            for (int i = 0; i < 4; i++) out[(rt * 16 + (lane >> 4) * 4 + i) * HP + col] = lrelu_s(acc[i]);
+                            for (int i = 0; i < 4; i++) out[(rt * 16 + (lane >> 4) * 4 + i) * HP + col] = toy_lrelu(acc[i]);
                         }
                     }
                     q += n;
@@ -175,10 +159,10 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
         const int s = tid;
         const size_t g = (size_t)b * a.S + (size_t)(s0 + s);
         if (a.samples != nullptr)
-            for (int c = 0; c < a.x_d; c++) a.samples[g * a.x_d + c] = su[3 * s + c];
+            for (int c = 0; c < a.flow.x_d; c++) a.samples[g * a.flow.x_d + c] = su[3 * s + c];
         if (a.y_dev != nullptr) {
             float d = 0.f;
-            for (int c = a.x_d; c < 3; c++) d += fabsf(su[3 * s + c] - yb[c - a.x_d]);
+            for (int c = a.flow.x_d; c < 3; c++) d += fabsf(su[3 * s + c] - yb[c - a.flow.x_d]);
             a.y_dev[g] = d;
         }
         if (a.hist != nullptr) {
@@ -186,7 +170,7 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
             // (a NaN or an infinity fails the comparisons)
             bool in = true;
             size_t idx = (size_t)b;
-            for (int c = 0; c < a.x_d; c++) {
+            for (int c = 0; c < a.flow.x_d; c++) {
                 const float w = floorf((su[3 * s + c] - a.lo[c]) * a.scale[c]);
                 in = in && w >= 0.f && w < (float)a.G;
                 idx = idx * (size_t)a.G + (size_t)(in ? (int)w : 0);
@@ -195,12 +179,12 @@ __global__ __launch_bounds__(BT) void k_toy_sample(ToySampleArgs a) {
         }
     }
     // the tile's shifted partial per component, folded in draw order
-    if (tid < a.x_d) {
+    if (tid < a.flow.x_d) {
         const int c = tid;
         float K = 0.f, S1 = 0.f, S2 = 0.f;
 #pragma unroll 8
         for (int s = 0; s < cnt; s++) sample_fold(su[3 * s + c], s == 0, K, S1, S2);
-        float* dst = a.part + (((size_t)b * a.tiles + tile) * a.x_d + c) * TOY_SAMPLE_PART;
+        float* dst = a.part + (((size_t)b * a.tiles + tile) * a.flow.x_d + c) * TOY_SAMPLE_PART;
         *reinterpret_cast<f4*>(dst) = f4{(float)cnt, K, S1, S2};
     }
 }
@@ -261,12 +245,12 @@ size_t toy_sample_lds_bytes(int H) { return ((size_t)2 * TS * toy_bwd_hp(H) + 5 
 
 void launch_toy_sample(const ToySampleArgs& a, hipStream_t st) {
     const dim3 g((unsigned)a.B * (unsigned)a.tiles), b(BT);
-    const size_t lds = toy_sample_lds_bytes(a.H);
-    if (a.H <= 16)
+    const size_t lds = toy_sample_lds_bytes(a.flow.H);
+    if (a.flow.H <= 16)
         hipLaunchKernelGGL(k_toy_sample<4>, g, b, lds, st, a);
-    else if (a.H <= 32)
+    else if (a.flow.H <= 32)
         hipLaunchKernelGGL(k_toy_sample<8>, g, b, lds, st, a);
-    else if (a.H <= 48)
+    else if (a.flow.H <= 48)
         hipLaunchKernelGGL(k_toy_sample<12>, g, b, lds, st, a);
     else
         hipLaunchKernelGGL(k_toy_sample<16>, g, b, lds, st, a);

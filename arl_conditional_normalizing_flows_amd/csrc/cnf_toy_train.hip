@@ -5,7 +5,7 @@
 //                   reverse of the order the forward executed them. Per layer both nets (b, then A)
 //                   are recomputed from the layer input k_toy saved; a net's hidden activations
 //                   ((L+1) x TS x H) stay in LDS while it is back-propagated. The H x H Dense layers
-//                   run on v_mfma_f32_16x16x4_f32 (exact fp32 products; mma_tile, cnf_toy_mma.h): the recompute
+//                   run on v_mfma_f32_16x16x4_f32 (exact fp32 products; mma_tile, cnf_toy_device.h): the recompute
 //                   [TS x H][H x H], the data gradient [TS x H][H x H]^T and the weight gradient
 //                   [(H+1) x TS][TS x H], whose row H is a row of ones (the bias gradient, which
 //                   follows the kernel in the canonical parameter order). The 1- and 2-wide first and
@@ -20,7 +20,7 @@
 #include <cstdint>
 
 #include "cnf_kernels.h"
-#include "cnf_toy_mma.h"
+#include "cnf_toy_device.h"
 
 namespace cnf {
 
@@ -31,7 +31,6 @@ constexpr int BT = 256;          // threads per workgroup (4 waves)
 constexpr int NW = BT / 64;
 constexpr int SMALL_FLOATS = 3 * TS + 3 * TS + 2 * TS + 4 * TS;   // su, dv, dout, d1[2]
 
-__device__ __forceinline__ float lrelu_f(float x) { return x >= 0.f ? x : LRELU_ALPHA * x; }
 // LeakyReLU'(pre) from the stored post-activation value: h > 0 <=> pre > 0 (alpha > 0); 1 if pre > 0
 // else alpha, as TF
 __device__ __forceinline__ float lrelu_dh(float h) { return h > 0.f ? 1.f : LRELU_ALPHA; }
@@ -45,7 +44,7 @@ struct Net {
 
 __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int H = a.H, L = a.L, HP = a.HP;
+    const int H = a.flow.H, L = a.flow.L, HP = a.HP;
     float* act = sm;                              // [L+1][TS][HP] post-activation hidden vectors
     float* gb = act + (size_t)(L + 1) * TS * HP;  // [2][TS][HP] d loss / d pre-activation, ping-pong
     float* su = gb + 2 * TS * HP;                 // [TS][3] the layer's input u
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
         float g = 0.f;
         if (s0 + s < a.B) {
             const float z = a.zy[(size_t)(s0 + s) * 3 + c];
-            if (c < a.x_d) {
+            if (c < a.flow.x_d) {
                 g = z;
             } else {
                 const float d = z - a.xy[(size_t)(s0 + s) * 3 + c];
@@ -76,26 +75,12 @@ __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
         dv[e] = g;
     }
 
-    for (int step = a.nl - 1; step >= 0; step--) {
-        const int j = a.order[a.nl - 1 - step];
-        const int t = j % 6;
-        int i1[2], i2[2], n1, n2;   // u1 / u2 index sets of mask type t (:149-163), as k_toy
-        if (t < 3) {
-            n1 = 1;
-            n2 = 2;
-            i1[0] = t;
-            i1[1] = 0;
-            i2[0] = t == 0 ? 1 : 0;
-            i2[1] = t == 2 ? 1 : 2;
-        } else {
-            n1 = 2;
-            n2 = 1;
-            i1[0] = t == 5 ? 1 : 0;
-            i1[1] = t == 3 ? 1 : 2;
-            i2[0] = 5 - t;
-            i2[1] = 0;
-        }
-        const int net_floats = (a.net_off[j + 1] - a.net_off[j]) / 2;
+    for (int step = a.flow.nl - 1; step >= 0; step--) {
+        const int j = a.flow.order[a.flow.nl - 1 - step];
+        const ToyMask m = toy_mask(j);   // u1 / u2 index sets (:149-163), as k_toy
+        const int n1 = m.n1, n2 = m.n2;
+        const int i1[2] = {m.i1[0], m.i1[1]}, i2[2] = {m.i2[0], m.i2[1]};
+        const int net_floats = (a.flow.net_off[j + 1] - a.flow.net_off[j]) / 2;
         __syncthreads();   // dv of the previous layer complete; su free
         for (int e = tid; e < 3 * TS; e += BT) {
             const int s = e / 3;
@@ -104,8 +89,8 @@ __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
         __syncthreads();
 
         for (int net = 0; net < 2; net++) {   // b, then A
-            const float* p = a.params + a.net_off[j] + net * net_floats;
-            float* gp = part + a.net_off[j] + net * net_floats;
+            const float* p = a.params + a.flow.net_off[j] + net * net_floats;
+            float* gp = part + a.flow.net_off[j] + net * net_floats;
             const int off_hid = n1 * H + H;                       // first hidden Dense
             const int off_last = off_hid + L * (H * H + H);       // last Dense: kernel [H][n2], bias [n2]
 
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
                 float y = p[n1 * H + o];
                 y = fmaf(su[3 * s + i1[0]], p[o], y);
                 if (n1 > 1) y = fmaf(su[3 * s + i1[1]], p[H + o], y);
-                act[s * HP + o] = lrelu_f(y);
+                act[s * HP + o] = toy_lrelu(y);
             }
             __syncthreads();
             // ---- recompute: hidden Dense layers, [TS x H][H x H] + bias
@@ -134,7 +119,7 @@ __global__ __launch_bounds__(BT) void k_toy_bwd(ToyBwdArgs a) {
                         [&](int kk, int c) { return (kk < H && ct * 16 + c < H) ? W[kk * H + ct * 16 + c] : 0.f; }, acc);
                     if (col < H) {
 #pragma unroll
-                        for (int r = 0; r < 4; r++) out[(rt * 16 + (lane >> 4) * 4 + r) * HP + col] = lrelu_f(acc[r]);
+                        for (int r = 0; r < 4; r++) out[(rt * 16 + (lane >> 4) * 4 + r) * HP + col] = toy_lrelu(acc[r]);
                     }
                 }
                 __syncthreads();
@@ -251,8 +236,8 @@ size_t toy_bwd_lds_bytes(int H, int L) {
 }
 
 void launch_toy_bwd(const ToyBwdArgs& a, hipStream_t st) {
-    const int tiles = (a.B + TS - 1) / TS;
-    hipLaunchKernelGGL(k_toy_bwd, dim3(tiles), dim3(BT), toy_bwd_lds_bytes(a.H, a.L), st, a);
+    const int tiles = (int)toy_tiles(a.B, TS);
+    hipLaunchKernelGGL(k_toy_bwd, dim3(tiles), dim3(BT), toy_bwd_lds_bytes(a.flow.H, a.flow.L), st, a);
 }
 
 __global__ __launch_bounds__(256) void k_toy_grad_sum(const float* __restrict__ part, int tiles, int n,

@@ -23,14 +23,13 @@
 #include <string>
 #include <vector>
 
+#include "cnf_api.h"
 #include "cnf_kernels.h"
 #include "cnf_plan.h"
 
 namespace cnf {
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 void hchk(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));

@@ -8,12 +8,10 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/cnf.h"
+#include "cnf_api.h"
 #include "cnf_device.h"
 
 namespace cnf {
-
-int set_error(int code, const char* msg);   // cnf_runtime.cpp (cnf_last_error)
 
 // LogitK (cnf_kernels.h) of the fudge factor a
 LogitK logit_consts(float a) {
