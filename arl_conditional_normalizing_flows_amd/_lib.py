@@ -51,6 +51,10 @@ class cnf_toy_sample_desc(C.Structure):
                 ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
 
 
+class cnf_toy_density_desc(C.Structure):
+    _fields_ = [('num_points', C.c_int), ('grid_bins', C.c_int), ('lo', C.c_float * 2), ('hi', C.c_float * 2)]
+
+
 # per-layer completion callback of cnf_flow_backward_ex (void (*)(void* user, int coupling_index))
 LAYER_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
 
@@ -101,6 +105,10 @@ _SIGS = [
     ('cnf_toy_sample_workspace_bytes', C.c_size_t, [C.POINTER(cnf_toy_desc), C.c_int, C.POINTER(cnf_toy_sample_desc)]),
     ('cnf_toy_sample', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, C.POINTER(cnf_toy_sample_desc), _F, _F, _F, _F, _F, _P,
                                  C.c_int, _P]),
+    ('cnf_toy_density_workspace_bytes', C.c_size_t, [C.POINTER(cnf_toy_desc), C.c_int,
+                                                     C.POINTER(cnf_toy_density_desc)]),
+    ('cnf_toy_density', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, C.POINTER(cnf_toy_density_desc), _F, _F, _F, _F,
+                                  _P, C.c_int, _P]),
     ('cnf_logit', C.c_int, [_F, _F, C.c_int64, C.c_float, C.c_int, _P]),
     ('cnf_sr_preprocess', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_down', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

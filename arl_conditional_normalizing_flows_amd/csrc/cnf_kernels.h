@@ -439,6 +439,27 @@ size_t toy_sample_lds_bytes(int H);   // dynamic LDS of k_toy_sample
 void launch_toy_sample(const ToySampleArgs& a, hipStream_t st);
 void launch_toy_sample_stats(const float* part, int B, int tiles, int S, int x_d, float* mean, float* std,
                              hipStream_t st);
+// k_toy_density / k_toy_density_mass (cnf_toy_density.hip, cnf_toy_density): one workgroup takes one tile of
+// TOY_SAMPLE_TS consecutive points of one condition from xy to its log-density in direction -1 (tile =
+// point / TOY_SAMPLE_TS; a condition's last tile is zero-padded) and leaves one log-sum-exp partial; the second
+// kernel merges the partials in tile order
+constexpr int TOY_DENSITY_PART = 2;   // floats per partial: (m, s)
+struct ToyDensityArgs {
+    const float* params;
+    const float* y;        // [B][3 - x_d]
+    const float* x;        // [B][N][x_d], or null: the centres of a grid of G bins per component
+    float* log_prob;       // [B][N] or null
+    float* y_dev;          // [B][N] or null
+    float* z;              // [B][N][x_d] or null
+    float* part;           // [B][tiles][TOY_DENSITY_PART], or null (log_mass not asked for)
+    int B, N, tiles, HP;
+    int G;                 // grid bins per component (0 with x)
+    float lo[2], step[2];  // centre i of component c: lo[c] + (i + 0.5) step[c]
+    ToyNet flow;
+};
+size_t toy_density_lds_bytes(int H);   // dynamic LDS of k_toy_density
+void launch_toy_density(const ToyDensityArgs& a, hipStream_t st);
+void launch_toy_density_mass(const float* part, int B, int tiles, double log_cell, float* log_mass, hipStream_t st);
 void launch_nll_sums(const float* per_image, float* sums, int B, hipStream_t st);
 void launch_net_lds(const NetLdsArgs& a, int B, int lds, hipStream_t st);
 int netlds_num_shapes();   // shape-specialised k_net_lds instantiations compiled in

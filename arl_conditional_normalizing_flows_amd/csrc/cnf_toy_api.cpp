@@ -1,6 +1,6 @@
 // cnf_toy_api.cpp — the C ABI of the TOYcINN dense flow (include/cnf.h cnf_toy_*): the descriptor checks, the
 // one description of the flow its kernels read (ToyNet, cnf_kernels.h) and the launches of k_toy (cnf_toy.hip),
-// k_toy_bwd (cnf_toy_train.hip) and k_toy_sample (cnf_toy_sample.hip).
+// k_toy_bwd (cnf_toy_train.hip), k_toy_sample (cnf_toy_sample.hip) and k_toy_density (cnf_toy_density.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -103,6 +103,32 @@ const char* toy_sample_desc_error(const cnf_toy_desc* d, int B, const cnf_toy_sa
         if (std::pow((double)s->hist_bins, d->x_d) * B > 1e12) return "hist_bins: the grid exceeds 10^12 cells";
     }
     return nullptr;
+}
+
+// points per condition of a density call (grid: G^x_d), or 0 with *err set: the argument errors of
+// cnf_toy_density that need no pointer but the descriptors; grid: whether the points are a grid's centres
+int64_t toy_density_points(const cnf_toy_desc* d, int B, const cnf_toy_density_desc* q, bool grid, const char** err) {
+    *err = nullptr;
+    if (q == nullptr) return *err = "null density descriptor", 0;
+    if (B < 1) return *err = "B must be >= 1", 0;
+    int64_t N = q->num_points;
+    if (!grid) {
+        if (q->grid_bins != 0) return *err = "grid_bins must be 0 when x is given", 0;
+        if (q->num_points < 1) return *err = "num_points must be >= 1", 0;
+    } else {
+        if (q->grid_bins < 1) return *err = "grid_bins must be >= 1 when x is null", 0;
+        for (int c = 0; c < d->x_d; c++) {
+            if (!std::isfinite(q->lo[c]) || !std::isfinite(q->hi[c])) return *err = "lo / hi must be finite", 0;
+            if (!(q->lo[c] < q->hi[c])) return *err = "lo must be below hi", 0;
+            const float step = (q->hi[c] - q->lo[c]) / (float)q->grid_bins;
+            if (!std::isfinite(step) || !(step > 0.f)) return *err = "lo / hi: the bin step is not a positive finite number", 0;
+        }
+        N = q->grid_bins;
+        if (d->x_d == 2) N *= q->grid_bins;
+    }
+    if (N > INT32_MAX || (int64_t)B * toy_tiles(N, TOY_SAMPLE_TS) > INT32_MAX || (double)B * (double)N * 3.0 > 4e18)
+        return *err = "B * N * 3 exceeds the index range (N and B * tiles must stay below 2^31)", 0;
+    return N;
 }
 
 }  // namespace
@@ -243,6 +269,69 @@ int cnf_toy_sample(const cnf_toy_desc* d, const float* params, const float* y, c
     if (mean || std) {
         launch_toy_sample_stats(a.part, B, a.tiles, a.S, x_d, mean, std, (hipStream_t)stream);
         hip_check(hipGetLastError(), "k_toy_sample_stats");
+    }
+    return CNF_OK;
+    CNF_CATCH
+}
+
+// ---- density (kernels: cnf_toy_density.hip) --------------------------------------------------------------
+size_t cnf_toy_density_workspace_bytes(const cnf_toy_desc* d, int B, const cnf_toy_density_desc* q) {
+    try {
+        toy_check(d);
+        const char* e = nullptr;
+        const int64_t N = toy_density_points(d, B, q, q != nullptr && q->grid_bins != 0, &e);
+        if (e) throw std::invalid_argument(e);
+        // the tile partials [B][tiles][TOY_DENSITY_PART]
+        return (size_t)B * (size_t)toy_tiles(N, TOY_SAMPLE_TS) * TOY_DENSITY_PART * sizeof(float);
+    } catch (const std::exception& e) {
+        fail(CNF_E_INVALID, std::string("cnf_toy_density_workspace_bytes: ") + e.what());
+        return 0;
+    }
+}
+
+int cnf_toy_density(const cnf_toy_desc* d, const float* params, const float* y, const float* x,
+                    const cnf_toy_density_desc* q, float* log_prob, float* y_dev, float* z, float* log_mass,
+                    void* workspace, int B, void* stream) {
+    CNF_TRY
+    toy_check(d);
+    if (!params || !workspace) return fail(CNF_E_INVALID, "cnf_toy_density: null params or workspace");
+    if (!y) return fail(CNF_E_INVALID, "cnf_toy_density: null y");
+    const char* e = nullptr;
+    const int64_t N = toy_density_points(d, B, q, x == nullptr, &e);
+    if (e) return fail(CNF_E_INVALID, std::string("cnf_toy_density: ") + e);
+    if (log_mass && x) return fail(CNF_E_INVALID, "cnf_toy_density: log_mass is defined for a grid only (x must be null)");
+    if (!log_prob && !y_dev && !z && !log_mass)
+        return fail(CNF_E_INVALID, "cnf_toy_density: no output requested (log_prob, y_dev, z, log_mass all null)");
+    if ((int64_t)toy_density_lds_bytes(d->intermediate_dims) > TOY_LDS_BUDGET)
+        return fail(CNF_E_INVALID, "cnf_toy_density: the hidden activations of a point tile exceed the 160 KiB LDS budget");
+    ToyDensityArgs a;
+    std::memset(&a, 0, sizeof(a));
+    toy_flow(d, a.flow);
+    const int x_d = a.flow.x_d;
+    a.params = params;
+    a.y = y;
+    a.x = x;
+    a.log_prob = log_prob;
+    a.y_dev = y_dev;
+    a.z = z;
+    a.part = log_mass ? static_cast<float*>(workspace) : nullptr;
+    a.B = B;
+    a.N = (int)N;
+    a.tiles = (int)toy_tiles(N, TOY_SAMPLE_TS);
+    a.HP = toy_bwd_hp(a.flow.H);
+    a.G = x ? 0 : q->grid_bins;
+    double log_cell = 0.0;
+    for (int c = 0; c < 2; c++) {
+        const bool on = !x && c < x_d;
+        a.lo[c] = on ? q->lo[c] : 0.f;
+        a.step[c] = on ? (q->hi[c] - q->lo[c]) / (float)q->grid_bins : 0.f;
+        if (on) log_cell += std::log((double)a.step[c]);
+    }
+    launch_toy_density(a, (hipStream_t)stream);
+    hip_check(hipGetLastError(), "k_toy_density");
+    if (log_mass) {
+        launch_toy_density_mass(a.part, B, a.tiles, log_cell, log_mass, (hipStream_t)stream);
+        hip_check(hipGetLastError(), "k_toy_density_mass");
     }
     return CNF_OK;
     CNF_CATCH

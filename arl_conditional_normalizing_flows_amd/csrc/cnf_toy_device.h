@@ -1,5 +1,5 @@
 // cnf_toy_device.h — what the toy flow's kernels share on the device (k_toy in cnf_toy.hip, k_toy_bwd in
-// cnf_toy_train.hip, k_toy_sample in cnf_toy_sample.hip): the coupling masks, LeakyReLU and the fp32
+// cnf_toy_train.hip, k_toy_sample in cnf_toy_sample.hip, k_toy_density in cnf_toy_density.hip): the coupling masks, LeakyReLU and the fp32
 // matrix-core tile. One definition each, so the kernels agree on the index sets, the operand maps and the k order.
 #pragma once
 

@@ -2,7 +2,7 @@
 
 Same constructor arguments, `call(u, direction=-1)` / `log_loss` / `compile` / `train_step` /
 `test_step` / `metrics` semantics as TOYcINN_make_model.py:105-506, on torch tensors [B, 3] fp32 on the ROCm device; the
-flow runs in libcnf_hip.so (k_toy, k_toy_bwd for the gradient, k_toy_sample for `sample`) through the C ABI. Note the toy's direction convention is the
+flow runs in libcnf_hip.so (k_toy, k_toy_bwd for the gradient, k_toy_sample for `sample`, k_toy_density for `log_prob` / `density`) through the C ABI. Note the toy's direction convention is the
 reverse of cFlow's: -1 maps xy' -> zy (training direction, returns the per-sample log-det),
 +1 maps zy -> xy'.
 
@@ -35,6 +35,17 @@ def _default_mask_indices(n: int, seed: int):
         out.extend(int(v) for v in blk)
     out.extend(range(6 * (n // 6), n))
     return out
+
+
+def _parse_box(G, lo, hi, x_d, what):
+    """(G, lo, hi) of a grid of G bins per component over [lo, hi): lo / hi scalars or one value per component,
+    returned as tuples padded to two components (cnf_toy_sample_desc.hist_lo, cnf_toy_density_desc.lo)."""
+    G = int(G)
+    lo = tuple(float(v) for v in (lo if isinstance(lo, (tuple, list)) else (lo,) * x_d))
+    hi = tuple(float(v) for v in (hi if isinstance(hi, (tuple, list)) else (hi,) * x_d))
+    if len(lo) != x_d or len(hi) != x_d:
+        raise ValueError(f'{what} lo / hi need one value per component ({x_d})')
+    return G, lo + (0.0,) * (2 - x_d), hi + (0.0,) * (2 - x_d)
 
 
 class cINN_affine:
@@ -167,14 +178,9 @@ class cINN_affine:
         G, lo, hi = 0, (0.0, 0.0), (0.0, 0.0)
         if hist is not None:
             G, lo, hi = hist
-            G = int(G)
-            lo = tuple(float(v) for v in (lo if isinstance(lo, (tuple, list)) else (lo,) * x_d))
-            hi = tuple(float(v) for v in (hi if isinstance(hi, (tuple, list)) else (hi,) * x_d))
-            if len(lo) != x_d or len(hi) != x_d:
-                raise ValueError(f'hist lo / hi need one value per component ({x_d})')
+            G, lo, hi = _parse_box(G, lo, hi, x_d, 'hist')
             if G < 1:
                 raise AssertionError('cINN_affine.sample: hist needs at least one bin')
-            lo, hi = lo + (0.0,) * (2 - x_d), hi + (0.0,) * (2 - x_d)
         desc = _lib.cnf_toy_sample_desc(S, float(temperature), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
                                         G, (C.c_float * 2)(*lo), (C.c_float * 2)(*hi))
         lib = _lib.load()
@@ -200,6 +206,100 @@ class cINN_affine:
         check(lib.cnf_toy_sample(C.byref(self._desc), ptr(self.params), ptr(y), C.byref(desc), ptr(out.get('samples')),
                                  ptr(out.get('mean')), ptr(out.get('std')), ptr(out.get('y_dev')), ptr(out.get('hist')),
                                  ptr(ws), B, _stream()), 'cnf_toy_sample')
+        return out
+
+    def _density(self, y, x, desc, N, shape, return_y_dev, return_z, log_mass, who):
+        """cnf_toy_density on y [B, 3 - x_d] and x [B, N, x_d] (or None: desc's grid); the per-point outputs
+        reshaped to [B, *shape]."""
+        lib = _lib.load()
+        B, x_d = int(y.shape[0]), self.x_d
+        key = ('density', B, N)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(lib.cnf_toy_density_workspace_bytes(C.byref(self._desc), B, C.byref(desc)))
+            if nbytes <= 0:   # an argument error, as the reference's asserts
+                raise AssertionError(f'cINN_affine.{who}: {lib.cnf_last_error().decode()}')
+            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        out = {'log_prob': torch.empty((B, N), device=y.device, dtype=torch.float32)}
+        if log_mass:
+            out['log_mass'] = torch.empty(B, device=y.device, dtype=torch.float32)
+        if return_y_dev:
+            out['y_dev'] = torch.empty((B, N), device=y.device, dtype=torch.float32)
+        if return_z:
+            out['z'] = torch.empty((B, N, x_d), device=y.device, dtype=torch.float32)
+        check(lib.cnf_toy_density(C.byref(self._desc), ptr(self.params), ptr(y), ptr(x), C.byref(desc),
+                                  ptr(out['log_prob']), ptr(out.get('y_dev')), ptr(out.get('z')), ptr(out.get('log_mass')),
+                                  ptr(ws), B, _stream()), 'cnf_toy_density')
+        for n in ('log_prob', 'y_dev'):
+            if n in out:
+                out[n] = out[n].reshape(B, *shape)
+        if 'z' in out:
+            out['z'] = out['z'].reshape(B, *shape, x_d)
+        return out
+
+    def _condition(self, y):
+        y = _as_input(y, 'y')
+        yd = self.io_shape - self.x_d
+        if y.dim() != 2 or y.shape[1] != yd:
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {yd}]')
+        return y
+
+    def log_prob(self, x, y, return_y_dev=False, return_z=False):
+        """The flow's exact log-density at given points, in one fused native call (cnf_toy_density, k_toy_density:
+        no [B*N, 3] tensor and no zy exist anywhere): log_prob = log N(z; 0, I) + log|det J| of xy -> zy, the llz +
+        log_detJ of log_loss per point. Where the model returns the condition (y_hat = y, a trained model) this is
+        log p(x | y).
+
+        x: [B, N, x_d] with y [B, 3 - x_d], or x [N, x_d] with y [3 - x_d] (one condition; the leading dimension
+        is squeezed on return). Returns log_prob [B, N], or with return_y_dev / return_z a dict of 'log_prob',
+        'y_dev' [B, N] (sum |y_hat - y| of each point, as sample's) and 'z' [B, N, x_d] (the latent image).
+
+        model.log_prob(model.sample(y, S)['samples'], y) is each draw's log-density (and its 'z' recovers the
+        draw's latent up to rounding). The values agree with call(xy, -1) up to rounding, not bit for bit (the
+        hidden layers run on the matrix cores); a point's bits depend only on the weights, its y and its
+        coordinates."""
+        x, y = _as_input(x, 'x'), _as_input(y, 'y')
+        one = x.dim() == 2 and y.dim() == 1
+        if one:
+            x, y = x.unsqueeze(0), y.unsqueeze(0)
+        y = self._condition(y)
+        if x.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != self.x_d:
+            raise ValueError(f'x has shape {tuple(x.shape)}, expected [{y.shape[0]}, None, {self.x_d}]')
+        N = int(x.shape[1])
+        desc = _lib.cnf_toy_density_desc(N, 0, (C.c_float * 2)(0.0, 0.0), (C.c_float * 2)(0.0, 0.0))
+        out = self._density(y, x, desc, N, (N,), return_y_dev, return_z, False, 'log_prob')
+        if one:
+            out = {n: t[0] for n, t in out.items()}
+        return out if (return_y_dev or return_z) else out['log_prob']
+
+    def density(self, y, G, lo, hi, return_y_dev=False, return_z=False):
+        """The flow's exact log-density of x given each condition y on a grid of G bins per component over
+        [lo, hi): the heat map of p(x | y), evaluated at the centres of the bins of sample(hist=(G, lo, hi)) (the
+        curve those counts converge to), in one fused native call (cnf_toy_density).
+
+        y: [B, 3 - x_d] on the device, or [3 - x_d] for one condition. lo / hi: scalars or one value per component,
+        as sample's hist. Returns a dict: 'log_prob' [B, G] or [B, G, G] (component 0 major, as 'hist'), 'log_mass'
+        [B] = log(sum exp(log_prob) * the cell volume), the share of the density inside the box (about 0 for a
+        trained model and a box that covers it), 'centers', a tuple of x_d fp32 tensors [G]: lo + (i + 0.5) *
+        ((hi - lo) / G) in fp32, one multiply and then one add; and with return_y_dev / return_z 'y_dev' (shaped
+        as 'log_prob') and 'z' [B, G(, G), x_d]. density(...) equals log_prob at the centres bit for bit."""
+        y = _as_input(y, 'y')
+        if y.dim() == 1:
+            y = y.unsqueeze(0)
+        y = self._condition(y)
+        x_d = self.x_d
+        G, lo, hi = _parse_box(G, lo, hi, x_d, 'density')
+        if G < 1:
+            raise AssertionError('cINN_affine.density: the grid needs at least one bin')
+        desc = _lib.cnf_toy_density_desc(0, G, (C.c_float * 2)(*lo), (C.c_float * 2)(*hi))
+        out = self._density(y, None, desc, G ** x_d, (G,) * x_d, return_y_dev, return_z, True, 'density')
+        idx = np.arange(G, dtype=np.float32) + np.float32(0.5)
+        centers = []
+        for c in range(x_d):
+            step = (np.float32(hi[c]) - np.float32(lo[c])) / np.float32(G)
+            centers.append(torch.from_numpy((np.float32(lo[c]) + (idx * step).astype(np.float32)).astype(np.float32))
+                           .to(y.device))
+        out['centers'] = tuple(centers)
         return out
 
     def log_loss(self, xy, process_group=None):

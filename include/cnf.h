@@ -434,6 +434,64 @@ int cnf_toy_sample(const cnf_toy_desc* d, const float* params, const float* y /*
                    const cnf_toy_sample_desc* s, float* samples, float* mean, float* std,
                    float* y_dev, uint32_t* hist, void* workspace, int B, void* stream);
 
+/* ---- TOYcINN density: the flow's exact log-density at N points per condition, for each of B
+ * conditions, in one fused launch: on the centres of a grid (the heat map of p(x | y), the curve
+ * the counts of cnf_toy_sample's hist converge to) or at given points.
+ *
+ * Points: with x == NULL, the centres of a grid of grid_bins = G bins per component over
+ * [lo[c], hi[c]), N = G^x_d: point p = i0 (x_d 1) or p = i0 * G + i1 (x_d 2, component 0 major, the
+ * layout of cnf_toy_sample's hist); component c of it is lo[c] + ((float)i_c + 0.5f) * step_c with
+ * step_c = (hi[c] - lo[c]) / (float)G, in fp32, one multiply and then one add, each rounded (no
+ * fused multiply-add), so the centres can be recomputed bit for bit; centre i lies in bin i of
+ * cnf_toy_sample's histogram over the same box. With x != NULL: x[B][N][x_d], N = num_points. The
+ * remaining 3 - x_d components of every point of condition b are y[b].
+ *
+ * The flow runs in direction -1 (cnf_toy_call's law: reverse layer order, u2 = exp(tanh A) u2 + b,
+ * log-det = the sum of tanh A, added layer by layer in execution order, within a layer output 0
+ * then output 1); the H x H Dense layers run on the fp32 matrix cores, so the results are
+ * cnf_toy_call(..., -1)'s up to rounding (the same bounds against the float64 model), not its bits.
+ *
+ * Per-point outputs, each may be NULL:
+ *   log_prob [B][N] = llz + log-det, llz = -x_d/2 log(2 pi) - 1/2 sum_{c < x_d} z_c^2 (the llz and
+ *                     log_detJ of cnf_toy_call's per_sample; what cnf_flow_sample calls log_prob).
+ *                     Where the flow returns the condition (y_hat = y, a trained model) the
+ *                     Jacobian is block-triangular and this is log p(x | y).
+ *   y_dev    [B][N] = sum over the 3 - x_d condition components of |y_hat - y|, as cnf_toy_sample's
+ *                     (lly = -lambda_y * y_dev)
+ *   z        [B][N][x_d], the latent image of the point
+ *
+ * log_mass [B] (grid only, may be NULL) = log( sum_p exp(log_prob_p) * prod_c step_c ): the share
+ * of the conditional density inside the box (about 0 for a trained model and a box that covers
+ * it). Point p belongs to tile t = p / 128. Per tile the kernel folds, in point order in fp32,
+ *   m_t = the largest finite log_prob of the tile,  s_t = sum_p expf(log_prob_p - m_t)
+ * and the partials are merged in tile order in fp64:
+ *   M = max_t m_t,  S = sum_t s_t exp(m_t - M),  log_mass = M + log S + sum_c log step_c
+ * rounded once to fp32. A tile without a finite value contributes nothing; a condition without one
+ * gives -inf; a NaN log_prob makes log_mass NaN. No atomics.
+ *
+ * Determinism: the bits of a point's log_prob, y_dev and z depend on (params, y[b], the point's
+ * fp32 coordinates) only: not on B, N, which tile or tile row the point sits in, or whether it came
+ * from the grid or from x. The bits of log_mass depend on (params, y[b], G, lo, hi) only. Nothing is
+ * read that the call did not write: the contents of the workspace and the outputs do not matter. */
+typedef struct cnf_toy_density_desc {
+    int   num_points;        /* N per condition when x != NULL; ignored for a grid */
+    int   grid_bins;         /* G >= 1 when x == NULL; must be 0 when x != NULL */
+    float lo[2], hi[2];      /* the grid's box per component, as cnf_toy_sample_desc.hist_lo / hist_hi */
+} cnf_toy_density_desc;
+
+/* Workspace bytes of cnf_toy_density: the tile partials [B][ceil(N / 128)] of 8 bytes each, whatever
+ * outputs are requested (grid_bins >= 1: N = G^x_d; grid_bins == 0: N = num_points). 0 for an
+ * invalid argument (cnf_last_error says which). */
+size_t cnf_toy_density_workspace_bytes(const cnf_toy_desc* d, int B, const cnf_toy_density_desc* q);
+
+/* CNF_E_INVALID before any HIP call for: NULL y, params, descriptor or workspace; B < 1; x given
+ * with num_points < 1 or grid_bins != 0; x NULL with grid_bins < 1, lo >= hi or a non-finite edge;
+ * log_mass with x given; no output requested; B * tiles >= 2^31 or B * N * 3 beyond the index range.
+ * No host read and no allocation: the call can be captured into a graph. */
+int cnf_toy_density(const cnf_toy_desc* d, const float* params, const float* y /* [B][3 - x_d] */,
+                    const float* x, const cnf_toy_density_desc* q, float* log_prob, float* y_dev, float* z,
+                    float* log_mass, void* workspace, int B, void* stream);
+
 /* ---- input transforms (the step before the path; conv_cINN_base_functions.py) ----------- */
 
 /* Logit preprocessing of preprocess_dataset_class(LOGITS=True) (:174-231), elementwise over n
