@@ -46,6 +46,11 @@ class cnf_sample_desc(C.Structure):
                 ('seed', C.c_uint64), ('offset', C.c_uint64), ('logit_a', C.c_float), ('residual', C.c_int)]
 
 
+class cnf_sample_score_desc(C.Structure):
+    _fields_ = [('bins', C.c_int), ('lo', C.c_float), ('hi', C.c_float), ('num_quantiles', C.c_int),
+                ('quantiles', C.c_float * 8)]
+
+
 class cnf_toy_sample_desc(C.Structure):
     _fields_ = [('num_samples', C.c_int), ('temperature', C.c_float), ('seed', C.c_uint64), ('offset', C.c_uint64),
                 ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
@@ -82,6 +87,8 @@ _SIGS = [
     ('cnf_flow_sample', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_flow_sample_logp', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), _F, _F, _F, _F, _F, _P, C.c_int,
                                        _P]),
+    ('cnf_flow_sample_score', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), C.POINTER(cnf_sample_score_desc),
+                                        _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_forward', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse_logdet', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),

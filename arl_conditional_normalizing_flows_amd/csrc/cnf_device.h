@@ -117,6 +117,14 @@ __device__ __forceinline__ float delogit_value(float v, const LogitK& k) {
     const float z = v * k.span + k.lo;
     return (1.f / (1.f + expf(-z)) - k.a) * k.inv_bc;
 }
+// the sampler's post-transform of one drawn x value: de_logitify if logit, then + y if residual. One
+// expression for the samples output (k_sample_fold) and the scores of the same draws (k_sample_score,
+// k_sample_sqerr), which therefore see the returned value bit for bit.
+__device__ __forceinline__ float sample_post_value(float v, int logit, const LogitK& k, int residual, float yv) {
+    if (logit) v = delogit_value(v, k);
+    if (residual) v = v + yv;
+    return v;
+}
 // Running statistics of the draws of one sampled element (cnf_flow_sample): the shifted sums the LN
 // partials use (ln_partial above), (K, S1, S2) with K the first draw's value, S1 = sum (v - K),
 // S2 = sum (v - K)^2 over the draws so far in draw order. The shift keeps S2 - S1^2/S from cancelling

@@ -592,6 +592,48 @@ void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* 
 // ld_part[nl][c.n][np] as the chunk's inverse wrote them (k_ld_reduce's order); one wave per image
 void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
                         hipStream_t st);
+// Scoring the draws against a truth (cnf_flow_sample_score). v below is k_sample_fold's sample value
+// (sample_post_value, cnf_device.h). The outputs are the state between chunks: a chunk that holds b's first
+// draw initialises b's entries, every other chunk loads them, so nothing is read that this call did not write.
+// k_sample_score: k_sample_fold's ownership (a workgroup owns a tile of elements of one condition b over the
+// chunk's draws of b). rank[b,p,c] += #{v < truth} (null: none); abs_err[b,p,c]: the fp32 running sum of
+// |v - truth| in draw order, divided by S with b's last draw (null: none); hist[b,p,c,k] += the draws with
+// k == (int)floorf((v - lo) * scale), 0 <= k < bins (null: none; out of range and NaN dropped).
+struct SampleScoreArgs {
+    const float* xy_hat;
+    const float* y;
+    const float* truth;   // [B][HW][x_d]; needed by rank and abs_err
+    int* rank;
+    float* abs_err;
+    int* hist;            // [B][HW][x_d][bins]
+    int logit, residual, bins;
+    float lo, scale;     // scale = (float)bins / (hi - lo)
+    LogitK lk;
+};
+constexpr int SCORE_MAX_BINS = 256, SCORE_MAX_QUANTILES = 8;
+void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStream_t st);
+// k_sample_sqerr: sq_err[g0 + i] = (float) sum_{p, c < x_d} ((double)v - (double)truth[(g0 + i) / S, p, c])^2,
+// one wave per image, fp64 lane sums in element order then the fixed-order wave sum
+struct SampleSqerrArgs {
+    const float* xy_hat;
+    const float* y;
+    const float* truth;
+    float* sq_err;        // [B][S]
+    int logit, residual;
+    LogitK lk;
+};
+void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st);
+// k_sample_quantiles, once after the last chunk, one thread per element: quantiles[j][b][p][c] of level q[j] from
+// hist by linear interpolation inside the bin where the cumulative count reaches q[j] * N; NaN where N == 0
+struct SampleQuantileArgs {
+    const int* hist;
+    float* quantiles;     // [nq][n]
+    long long n;          // B * HW * x_d
+    int bins, nq;
+    float lo, hi;
+    float q[SCORE_MAX_QUANTILES];
+};
+void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st);
 
 
 // ---- training (cnf_train.hip) -------------------------------------------------------------------

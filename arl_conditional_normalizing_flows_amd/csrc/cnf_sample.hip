@@ -5,7 +5,11 @@
 //   k_sample_fold  one pass over a chunk's xy_hat: post-transform, samples, running (K, S1, S2), mean / std
 //   k_sample_ydev  per image sum |y_hat - y|
 //   k_sample_logp  per image log-density of the draw: the prior's log N(z; 0, I) plus the inverse's log-det slots
-// All HBM-bound element / reduction kernels; no atomics, every sum in a fixed order.
+//   k_sample_score      the draws against a truth per element: rank, mean |error|, histogram (cnf_flow_sample_score)
+//   k_sample_sqerr      per image sum (sample - truth)^2
+//   k_sample_quantiles  per element quantiles from the finished histogram
+// All HBM-bound element / reduction kernels; no global atomics (k_sample_score counts with integer LDS adds
+// inside the tile its workgroup owns), every floating-point sum in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -91,9 +95,7 @@ __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldAr
 #pragma unroll
         for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
             const int s = sb + l + j * FOLD_L;
-            float v = w[j];
-            if (a.logit) v = delogit_value(v, a.lk);
-            if (a.residual) v = v + yv;
+            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, yv);
             if (valid && s < s1 && a.samples != nullptr) a.samples[(size_t)(gb + s) * per + pc] = v;
             if (stats) sh[l + j * FOLD_L][e] = v;
         }
@@ -162,6 +164,157 @@ __global__ __launch_bounds__(256) void k_sample_logp(SampleChunk q, const float*
     if (lane == 0) log_prob[q.g0 + i] = (float)(-0.5 * s - 0.5 * (double)n * LOG_2PI_D + L);
 }
 
+// k_sample_score's LDS: the histogram tile [bins][SCORE_EP], a bin's FOLD_E counters side by side and one pad
+// word per row (the adds of a half wave go to FOLD_E different banks whatever their bins, and the write-out,
+// which walks the tile in the output's [element][bin] order, meets a bank twice at the most); then the batch's
+// values [FOLD_BATCH][FOLD_E] for the serial abs_err fold and the draw lanes' counts [FOLD_L][FOLD_E]
+constexpr int SCORE_EP = FOLD_E + 1;
+size_t score_lds_bytes(int bins) { return ((size_t)bins * SCORE_EP + FOLD_BATCH * FOLD_E + FOLD_L * FOLD_E) * 4; }
+
+// k_sample_fold's ownership and batches. Every thread (e, l) takes the draws l, l + FOLD_L, ... of a batch:
+// it counts those below the truth and adds their bins to the LDS tile (integer LDS adds: order-free);
+// thread (e, 0) folds |v - truth| over the batch in draw order. The chunk's counts then go to the outputs,
+// which the workgroup owns: added to what the earlier chunks left there, or stored when the chunk holds
+// b's first draw. s0, s1 and the null tests are the same for the whole workgroup: the barriers are uniform.
+__global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScoreArgs a, long long b0, int bpc) {
+    extern __shared__ __align__(16) int score_lds[];
+    int* hs = score_lds;
+    float* sh = reinterpret_cast<float*>(score_lds + a.bins * SCORE_EP);
+    int* rk = score_lds + a.bins * SCORE_EP + FOLD_BATCH * FOLD_E;
+    const int per = q.HW * q.x_d;   // elements per condition
+    const long long b = b0 + blockIdx.x / bpc;
+    const int e = threadIdx.x % FOLD_E, l = threadIdx.x / FOLD_E;
+    const int pc0 = (blockIdx.x % bpc) * FOLD_E, pc = pc0 + e;
+    const bool valid = pc < per;
+    const int p = pc / q.x_d, c = pc - p * q.x_d;
+    const long long gb = b * q.S, g1 = q.g0 + q.n;
+    const int s0 = (int)((q.g0 > gb ? q.g0 : gb) - gb);
+    const int s1 = (int)((g1 < gb + q.S ? g1 : gb + q.S) - gb);
+    const bool first = s0 == 0;
+    const size_t se = (size_t)b * per + pc;
+    const bool owner = valid && l == 0;
+    const bool errs = a.abs_err != nullptr, hist = a.hist != nullptr;
+    const float yv = a.residual && valid ? a.y[se] : 0.f;
+    const float tv = a.truth != nullptr && valid ? a.truth[se] : 0.f;
+    float acc = errs && owner && !first ? a.abs_err[se] : 0.f;
+    int below = 0;
+    if (hist) {
+        for (int i = threadIdx.x; i < a.bins * SCORE_EP; i += 256) hs[i] = 0;
+        __syncthreads();
+    }
+    const size_t img = (size_t)q.HW * q.D;
+    const float* __restrict__ src = a.xy_hat + (size_t)p * q.D + c;   // the element in image 0 of the chunk
+    for (int sb = s0; sb < s1; sb += FOLD_BATCH) {
+        float w[FOLD_BATCH / FOLD_L];
+#pragma unroll
+        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
+            const int s = sb + l + j * FOLD_L;
+            w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
+        }
+#pragma unroll
+        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
+            const int s = sb + l + j * FOLD_L;
+            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, yv);
+            if (valid && s < s1) {
+                below += v < tv ? 1 : 0;
+                if (hist) {
+                    // k_toy_sample's expression; a NaN or an infinity fails the comparisons
+                    const float k = floorf((v - a.lo) * a.scale);
+                    if (k >= 0.f && k < (float)a.bins) atomicAdd(&hs[(int)k * SCORE_EP + e], 1);
+                }
+            }
+            if (errs) sh[(l + j * FOLD_L) * FOLD_E + e] = v;
+        }
+        if (!errs) continue;
+        __syncthreads();
+        if (owner) {
+            const int nk = s1 - sb < FOLD_BATCH ? s1 - sb : FOLD_BATCH;
+#pragma unroll 8
+            for (int k = 0; k < nk; k++) acc += fabsf(sh[k * FOLD_E + e] - tv);
+        }
+        __syncthreads();
+    }
+    if (errs && owner) a.abs_err[se] = s1 < q.S ? acc : acc / (float)q.S;
+    if (a.rank != nullptr) {
+        rk[l * FOLD_E + e] = below;
+        __syncthreads();
+        if (owner) {
+            int r = first ? 0 : a.rank[se];
+#pragma unroll
+            for (int k = 0; k < FOLD_L; k++) r += rk[k * FOLD_E + e];
+            a.rank[se] = r;
+        }
+    }
+    if (!hist) return;
+    __syncthreads();
+    // the tile's elements pc0 .. pc0 + ne - 1 are ne * bins consecutive counters of the output
+    const int ne = per - pc0 < FOLD_E ? per - pc0 : FOLD_E;
+    int* __restrict__ out = a.hist + ((size_t)b * per + pc0) * a.bins;
+    for (int i = threadIdx.x; i < ne * a.bins; i += 256) {
+        const int ee = i / a.bins, k = i - ee * a.bins;
+        int h = hs[k * SCORE_EP + ee];
+        if (!first) h += out[i];
+        out[i] = h;
+    }
+}
+
+// one wave per image of the chunk, as k_sample_ydev
+__global__ __launch_bounds__(256) void k_sample_sqerr(SampleChunk q, SampleSqerrArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= q.n) return;   // (whole waves)
+    const long long g = q.g0 + i;
+    const long long b = g / q.S;
+    const int n = q.HW * q.x_d;
+    const float* __restrict__ xi = a.xy_hat + (size_t)i * q.HW * q.D;
+    const float* __restrict__ tb = a.truth + (size_t)b * n;
+    const float* __restrict__ yb = a.y + (size_t)b * n;   // (read with residual only: y[b] has x's shape)
+    double s = 0.0;
+    for (int e = lane; e < n; e += 64) {
+        const int p = e / q.x_d, c = e - p * q.x_d;
+        const float yv = a.residual ? yb[e] : 0.f;
+        const float v = sample_post_value(xi[(size_t)p * q.D + c], a.logit, a.lk, a.residual, yv);
+        const double d = (double)v - (double)tb[e];
+        s += d * d;
+    }
+    s = wave_sum(s);
+    if (lane == 0) a.sq_err[g] = (float)s;
+}
+
+// One thread per element: N, then one walk over the bins that serves every level. Level q's bin is the first
+// with cumulative count C_k >= q N and C_k > 0 (so hist[k] > 0), its value the point of that bin where a
+// uniform spread of the bin's draws reaches q N; clamped to [lo, hi], which only the rounding of the
+// edges can leave. q <= 1 keeps q N <= N, so every level is met at the last occupied bin at the latest.
+__global__ __launch_bounds__(256) void k_sample_quantiles(SampleQuantileArgs a) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long long)gridDim.x * 256) {
+        const int* __restrict__ h = a.hist + (size_t)i * a.bins;
+        int N = 0;
+        for (int k = 0; k < a.bins; k++) N += h[k];
+        if (N == 0) {
+            for (int j = 0; j < a.nq; j++) a.quantiles[(size_t)j * a.n + i] = __builtin_nanf("");
+            continue;
+        }
+        float target[SCORE_MAX_QUANTILES];
+#pragma unroll
+        for (int j = 0; j < SCORE_MAX_QUANTILES; j++) target[j] = a.q[j] * (float)N;
+        unsigned done = 0;
+        int C = 0;
+        for (int k = 0; k < a.bins; k++) {
+            const int hk = h[k];
+            if (hk == 0) continue;
+#pragma unroll
+            for (int j = 0; j < SCORE_MAX_QUANTILES; j++) {
+                if (j < a.nq && !(done >> j & 1u) && (float)(C + hk) >= target[j]) {
+                    const float v = a.lo + ((float)k + (target[j] - (float)C) / (float)hk) * (a.hi - a.lo) / (float)a.bins;
+                    a.quantiles[(size_t)j * a.n + i] = fminf(fmaxf(v, a.lo), a.hi);
+                    done |= 1u << j;
+                }
+            }
+            C += hk;
+        }
+    }
+}
+
 int grid_for(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
@@ -196,6 +349,21 @@ void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* 
 void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
                         hipStream_t st) {
     CNF_LAUNCH(k_sample_logp, dim3((c.n + 3) / 4), dim3(256), 0, st, c, zy, ld_part, nl, np, log_prob);
+}
+
+void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStream_t st) {
+    const long long b0 = c.g0 / c.S, b1 = (c.g0 + c.n - 1) / c.S;
+    const int nb = (int)(b1 - b0 + 1);
+    const int bpc = (c.HW * c.x_d + FOLD_E - 1) / FOLD_E;   // workgroups per condition
+    CNF_LAUNCH(k_sample_score, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
+}
+
+void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st) {
+    CNF_LAUNCH(k_sample_sqerr, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
+}
+
+void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st) {
+    CNF_LAUNCH(k_sample_quantiles, dim3(grid_for(a.n)), dim3(256), 0, st, a);
 }
 
 }  // namespace cnf

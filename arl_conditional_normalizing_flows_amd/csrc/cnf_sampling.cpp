@@ -48,18 +48,56 @@ const char* sample_desc_error(const Plan& p, int B, const cnf_sample_desc* s) {
     return nullptr;
 }
 
-// the body of cnf_flow_sample (log_prob null: its launches, exactly) and cnf_flow_sample_logp
+// the score arguments of cnf_flow_sample_score (every output null: cnf_flow_sample_logp)
+struct ScoreArgs {
+    const cnf_sample_score_desc* sd = nullptr;
+    const float* truth = nullptr;
+    int* rank = nullptr;
+    float* abs_err = nullptr;
+    float* sq_err = nullptr;
+    int* hist = nullptr;
+    float* quantiles = nullptr;
+    bool any() const { return rank || abs_err || sq_err || hist || quantiles; }
+};
+
+// the argument errors of the score part (no output given: none)
+const char* score_error(const ScoreArgs& sc) {
+    if (!sc.any()) return nullptr;
+    const cnf_sample_score_desc* sd = sc.sd;
+    if (sd == nullptr) return "null score descriptor";
+    if ((sc.rank || sc.abs_err || sc.sq_err) && !sc.truth) return "rank, abs_err and sq_err need truth";
+    if (sc.quantiles && !sc.hist) return "quantiles needs hist";
+    if (sc.hist && sd->bins == 0) return "hist needs bins != 0";
+    if (sd->bins != 0) {
+        if (sd->bins < 2 || sd->bins > SCORE_MAX_BINS) return "bins must be in 2..256";
+        if (!std::isfinite(sd->lo) || !std::isfinite(sd->hi)) return "lo and hi must be finite";
+        if (!(sd->lo < sd->hi)) return "lo must be below hi";
+        if (!std::isfinite((float)sd->bins / (sd->hi - sd->lo))) return "lo / hi: the bin scale is not finite";
+    }
+    if (sc.quantiles) {
+        if (sd->num_quantiles < 1 || sd->num_quantiles > SCORE_MAX_QUANTILES) return "num_quantiles must be in 1..8";
+        for (int j = 0; j < sd->num_quantiles; j++)
+            if (!(sd->quantiles[j] >= 0.f && sd->quantiles[j] <= 1.f)) return "quantiles: every level must be in [0, 1]";
+    }
+    return nullptr;
+}
+
+// the body of cnf_flow_sample (log_prob null: its launches, exactly), cnf_flow_sample_logp and
+// cnf_flow_sample_score (every score output null: cnf_flow_sample_logp's launches, exactly)
 int flow_sample(const char* who, cnf_plan* plan, const float* params, const float* aux, const float* y,
                 const cnf_sample_desc* desc, float* samples, float* mean, float* std, float* y_dev, float* log_prob,
-                void* workspace, int B, void* stream) {
+                void* workspace, int B, void* stream, const ScoreArgs& sc = ScoreArgs()) {
     OptScope os_(plan ? &plan->p->opts : nullptr);
     const std::string w(who);
     if (!plan || !params || !aux || !workspace) return fail(CNF_E_INVALID, w + ": null argument");
     if (!y) return fail(CNF_E_INVALID, w + ": null y");
     if (const char* e = sample_desc_error(*plan->p, B, desc)) return fail(CNF_E_INVALID, w + ": " + e);
-    if (!samples && !mean && !std && !y_dev && !log_prob)
+    if (const char* e = score_error(sc)) return fail(CNF_E_INVALID, w + ": " + e);
+    if (!samples && !mean && !std && !y_dev && !log_prob && !sc.any())
         return fail(CNF_E_INVALID, w + ": no output requested (samples, mean, std, y_dev" +
-                                       (w == "cnf_flow_sample" ? "" : ", log_prob") + " all null)");
+                                       (w == "cnf_flow_sample" ? "" : ", log_prob") +
+                                       (w == "cnf_flow_sample_score" ? ", rank, abs_err, sq_err, hist, quantiles" : "") +
+                                       " all null)");
     CNF_TRY
     Plan& p = *plan->p;
     const cnf_flow_desc& d = p.desc;
@@ -82,6 +120,25 @@ int flow_sample(const char* who, cnf_plan* plan, const float* params, const floa
     fa.logit = desc->logit_a != 0.f ? 1 : 0;
     fa.residual = desc->residual != 0 ? 1 : 0;
     if (fa.logit) fa.lk = logit_consts(desc->logit_a);
+    const int per = d.io_h * d.io_w * d.x_d;   // elements per condition
+    const bool scores = sc.rank || sc.abs_err || sc.hist;
+    SampleScoreArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    sa.xy_hat = xy;
+    sa.y = y;
+    sa.truth = sc.truth;
+    sa.rank = sc.rank;
+    sa.abs_err = sc.abs_err;
+    sa.hist = sc.hist;
+    sa.logit = fa.logit;
+    sa.residual = fa.residual;
+    sa.lk = fa.lk;
+    if (sc.hist) {
+        sa.bins = sc.sd->bins;
+        sa.lo = sc.sd->lo;
+        sa.scale = (float)sc.sd->bins / (sc.sd->hi - sc.sd->lo);
+    }
+    const SampleSqerrArgs qa{xy, y, sc.truth, sc.sq_err, fa.logit, fa.residual, fa.lk};
     const float T = desc->temperature;
     const unsigned long long seed = desc->seed, off = desc->offset;
     const long long total = (long long)B * desc->num_samples;
@@ -109,6 +166,31 @@ int flow_sample(const char* who, cnf_plan* plan, const float* params, const floa
             E.record("k_sample_logp", 0, 4.0 * n * px * d.x_d + 8.0 * n * nl * np,
                      [=](void* st) { launch_sample_logp(c, zy, ld, nl, np, log_prob, (hipStream_t)st); });
         }
+        if (scores) {
+            // xy_hat once; per touched condition the truth and the read-modify-write of the outputs
+            const double nb = (double)((g0 + n - 1) / desc->num_samples - g0 / desc->num_samples + 1);
+            const double rmw = (sc.rank ? 8.0 : 0.0) + (sc.abs_err ? 8.0 : 0.0) + (sc.hist ? 8.0 * sa.bins : 0.0);
+            E.record("k_sample_score", 0, 4.0 * n * px * d.x_d + nb * per * ((sc.truth ? 4.0 : 0.0) + rmw),
+                     [=](void* st) { launch_sample_score(c, sa, (hipStream_t)st); });
+        }
+        if (sc.sq_err != nullptr)
+            E.record("k_sample_sqerr", 0, 8.0 * n * px * d.x_d,
+                     [=](void* st) { launch_sample_sqerr(c, qa, (hipStream_t)st); });
+    }
+    if (sc.quantiles != nullptr) {
+        SampleQuantileArgs ua;
+        std::memset(&ua, 0, sizeof(ua));
+        ua.hist = sc.hist;
+        ua.quantiles = sc.quantiles;
+        ua.n = (long long)B * per;
+        ua.bins = sc.sd->bins;
+        ua.nq = sc.sd->num_quantiles;
+        ua.lo = sc.sd->lo;
+        ua.hi = sc.sd->hi;
+        for (int j = 0; j < ua.nq; j++) ua.q[j] = sc.sd->quantiles[j];
+        Exec E{p, params, aux, ws, p.layout(1), 1, (hipStream_t)stream};
+        E.record("k_sample_quantiles", 0, 4.0 * (double)ua.n * (ua.bins + ua.nq),   // (the second walk hits the cache)
+                 [=](void* st) { launch_sample_quantiles(ua, (hipStream_t)st); });
     }
     check_launch();
     return CNF_OK;
@@ -141,6 +223,23 @@ int cnf_flow_sample_logp(cnf_plan* plan, const float* params, const float* aux, 
                          float* log_prob, void* workspace, int B, void* stream) {
     return flow_sample("cnf_flow_sample_logp", plan, params, aux, y, desc, samples, mean, std, y_dev, log_prob,
                        workspace, B, stream);
+}
+
+int cnf_flow_sample_score(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                          const cnf_sample_desc* desc, const cnf_sample_score_desc* score, const float* truth,
+                          float* samples, float* mean, float* std, float* y_dev, float* log_prob, int* rank,
+                          float* abs_err, float* sq_err, int* hist, float* quantiles, void* workspace, int B,
+                          void* stream) {
+    ScoreArgs sc;
+    sc.sd = score;
+    sc.truth = truth;
+    sc.rank = rank;
+    sc.abs_err = abs_err;
+    sc.sq_err = sq_err;
+    sc.hist = hist;
+    sc.quantiles = quantiles;
+    return flow_sample("cnf_flow_sample_score", plan, params, aux, y, desc, samples, mean, std, y_dev, log_prob,
+                       workspace, B, stream, sc);
 }
 
 }  // extern "C"

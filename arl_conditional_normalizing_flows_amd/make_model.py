@@ -567,7 +567,8 @@ class cFlow:
 
     # -- sampling -------------------------------------------------------------------------------
     def sample(self, y, num_samples, temperature=1.0, seed=0, offset=0, chunk=None, logit_a=None, residual=False,
-               return_samples=True, return_stats=True, return_y_dev=False, return_log_prob=False):
+               return_samples=True, return_stats=True, return_y_dev=False, return_log_prob=False, truth=None,
+               hist=None, quantiles=None, return_sq_err=None):
         """num_samples draws of x given each condition y and their per-pixel statistics: the recipe of
         TOYcINN.py:807-817 (z from the prior, concat y, the model in the generative direction, :1774-1798)
         with the post-transforms and the reduction over the draws, in one native call (cnf_flow_sample).
@@ -584,7 +585,19 @@ class cFlow:
         return_log_prob=True adds 'log_prob' [B,S]: the model's log-density of each draw in the flow's input
         space (before de_logitify / residual), llz + the sum of every coupling's s, i.e. what nll_sums reports
         as llz + logdet for that draw's (xy_hat, zy) -- from the inverse's own s (cnf_flow_sample_logp), for
-        ranking the draws of a condition, importance weights or typicality checks. It may be the only output."""
+        ranking the draws of a condition, importance weights or typicality checks. It may be the only output.
+
+        Scoring the draws in the same call, without the [B,S,...] tensor (cnf_flow_sample_score; with none of
+        these arguments the call is the one above):
+        truth [B,H,W,x_d] (or [H,W,x_d]), in the space of the returned samples (after de_logitify and the
+        residual), adds 'rank' (int32 [B,H,W,x_d]: how many of the S draws lie below the truth; uniform on
+        0..S for a calibrated model), 'abs_err' ([B,H,W,x_d]: the mean |draw - truth|) and 'sq_err' ([B,S]:
+        the sum over the image of (draw - truth)^2, i.e. which draw is closest; return_sq_err=False leaves it out).
+        hist=(bins, lo, hi), 2 <= bins <= 256, adds 'hist' (int32 [B,H,W,x_d,bins]: the draws per bin of
+        [lo, hi); draws outside are not counted) and 'hist_centers' [bins].
+        quantiles=(0.05, 0.5, 0.95) (up to 8 levels in [0, 1]; needs hist) adds 'quantiles' [Q,B,H,W,x_d], read
+        off the histogram by interpolation inside a bin: within one bin width of the draws' own quantile, NaN
+        where no draw fell into [lo, hi). Like everything else here they do not depend on chunk, bit for bit."""
         y = _as_input(y, 'y')
         H, W, D = self.io_shape
         if y.dim() == 3:
@@ -614,6 +627,10 @@ class cFlow:
             out['mean'], out['std'] = new(B, H, W, self.x_d), new(B, H, W, self.x_d)
         if return_y_dev:
             out['y_dev'] = new(B, max(S, 0))
+        if truth is not None or hist is not None or quantiles is not None:
+            if return_log_prob:
+                out['log_prob'] = new(B, max(S, 0))
+            return self._sample_score(y, desc, ws, out, truth, hist, quantiles, return_sq_err)
         if return_log_prob:
             out['log_prob'] = new(B, max(S, 0))
             check(lib.cnf_flow_sample_logp(self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc),
@@ -625,6 +642,49 @@ class cFlow:
                                   ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')),
                                   ptr(out.get('y_dev')), ptr(ws), B, _stream()),
               'cnf_flow_sample')
+        return out
+
+    def _sample_score(self, y, desc, ws, out, truth, hist, quantiles, return_sq_err):
+        """sample()'s call with a truth, a histogram box or quantile levels (cnf_flow_sample_score): adds the
+        score outputs to `out`, the dict of the plain outputs already allocated."""
+        H, W, D = self.io_shape
+        B, S, x_d = int(y.shape[0]), int(desc.num_samples), self.x_d
+        sd = _lib.cnf_sample_score_desc()
+        if truth is not None:
+            truth = _as_input(truth, 'truth')
+            if truth.dim() == 3:
+                truth = truth.unsqueeze(0)
+            if tuple(truth.shape) != (B, H, W, x_d):
+                raise ValueError(f'truth has shape {tuple(truth.shape)}, expected [{B}, {H}, {W}, {x_d}]')
+            out['rank'] = torch.empty((B, H, W, x_d), device=y.device, dtype=torch.int32)
+            out['abs_err'] = torch.empty((B, H, W, x_d), device=y.device, dtype=torch.float32)
+            if return_sq_err is None or return_sq_err:
+                out['sq_err'] = torch.empty((B, max(S, 0)), device=y.device, dtype=torch.float32)
+        elif return_sq_err:
+            raise AssertionError('cFlow.sample: return_sq_err needs truth')
+        if hist is not None:
+            bins, lo, hi = hist
+            sd.bins, sd.lo, sd.hi = int(bins), float(lo), float(hi)
+            if not 2 <= sd.bins <= 256:   # (before the allocation below is sized by it)
+                raise AssertionError(f'cFlow.sample: hist bins must be in 2..256, got {bins}')
+            out['hist'] = torch.empty((B, H, W, x_d, sd.bins), device=y.device, dtype=torch.int32)
+            k = torch.arange(sd.bins, device=y.device, dtype=torch.float32)
+            out['hist_centers'] = sd.lo + (k + 0.5) * ((sd.hi - sd.lo) / sd.bins)
+        if quantiles is not None:
+            if hist is None:
+                raise AssertionError('cFlow.sample: quantiles needs hist=(bins, lo, hi)')
+            levels = [float(q) for q in quantiles]
+            if not 1 <= len(levels) <= 8:
+                raise AssertionError(f'cFlow.sample: 1..8 quantile levels, got {len(levels)}')
+            sd.num_quantiles = len(levels)
+            for j, q in enumerate(levels):
+                sd.quantiles[j] = q
+            out['quantiles'] = torch.empty((len(levels), B, H, W, x_d), device=y.device, dtype=torch.float32)
+        check(_lib.load().cnf_flow_sample_score(
+            self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc), C.byref(sd), ptr(truth),
+            ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')), ptr(out.get('y_dev')),
+            ptr(out.get('log_prob')), ptr(out.get('rank')), ptr(out.get('abs_err')), ptr(out.get('sq_err')),
+            ptr(out.get('hist')), ptr(out.get('quantiles')), ptr(ws), B, _stream()), 'cnf_flow_sample_score')
         return out
 
     # -- loss -----------------------------------------------------------------------------------

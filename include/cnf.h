@@ -234,6 +234,43 @@ int cnf_flow_sample_logp(cnf_plan* plan, const float* params, const float* aux, 
                          const cnf_sample_desc* desc, float* samples, float* mean, float* std,
                          float* y_dev, float* log_prob, void* workspace, int B, void* stream);
 
+/* Scoring the draws against a truth inside the sampling call: where the truth ranks among the draws of
+ * its element, the per-element distribution of the draws, and how far each draw is from the truth,
+ * without a [B][S][...] tensor. v below is the value `samples` holds for (b, s, p, c) (after de_logitify
+ * and the residual), bit for bit; truth [B][H][W][x_d] lives in that space.
+ *   rank[b,p,c]     int32: the number of draws with v < truth (strict, fp32). Uniform on 0..S for a
+ *                   calibrated model (the rank / PIT histogram).
+ *   abs_err[b,p,c]  the mean over the draws of |v - truth|: an fp32 sum in draw order, divided by S.
+ *   sq_err[b,s]     (float) sum_{p,c} ((double)v - (double)truth)^2 of that draw: which draw is closest.
+ *   hist[b,p,c,k]   int32, k < bins: the draws with k == (int)floorf((v - lo) * scale), scale =
+ *                   (float)bins / (hi - lo) in fp32 (cnf_toy_sample's expression); draws outside
+ *                   [lo, hi) and NaN are not counted, so sum_k hist <= S.
+ *   quantiles[j,b,p,c]  for level q = quantiles[j] of the descriptor, from hist: N = sum_k hist[k],
+ *                   target = q * N (fp32), k the first bin with cumulative count C_k >= target and
+ *                   C_k > 0, value lo + (k + (target - C_{k-1}) / hist[k]) * (hi - lo) / bins, clamped to
+ *                   [lo, hi]; within one bin width of the inverted-CDF quantile of the counted draws.
+ *                   NaN where N == 0.
+ * The outputs are the state between chunks (the chunk holding b's first draw initialises b's entries), so
+ * the workspace is cnf_flow_sample's, nothing depends on what the buffers held, and no result depends on
+ * chunk, bit for bit. */
+typedef struct cnf_sample_score_desc {
+    int bins;               /* 0: no histogram; else 2..256 */
+    float lo, hi;           /* finite, lo < hi, when bins != 0 */
+    int num_quantiles;      /* 0..8; needs bins != 0 */
+    float quantiles[8];     /* each in [0, 1] */
+} cnf_sample_score_desc;
+
+/* cnf_flow_sample_logp plus the score outputs, each may be NULL; with all of them NULL (score may then
+ * be NULL too) the launches are cnf_flow_sample_logp's. CNF_E_INVALID before any HIP call, besides
+ * cnf_flow_sample's cases, for: a NULL score descriptor with a score output given; rank, abs_err or
+ * sq_err without truth; hist with bins == 0; bins outside 2..256; lo or hi not finite or lo >= hi;
+ * quantiles without hist, num_quantiles outside 1..8, or a level outside [0, 1] or NaN. */
+int cnf_flow_sample_score(cnf_plan* plan, const float* params, const float* aux, const float* y,
+                          const cnf_sample_desc* desc, const cnf_sample_score_desc* score,
+                          const float* truth, float* samples, float* mean, float* std, float* y_dev,
+                          float* log_prob, int* rank, float* abs_err, float* sq_err, int* hist,
+                          float* quantiles, void* workspace, int B, void* stream);
+
 /* coupling_layer.forward_and_Jacobian (:1258-1328) for layer `layer` of
  * layers_list: u -> v (shape of the layer's in_shape); logdet_accum[B] +=
  * per-image sum of A(u1) (pass NULL to skip). u and v must not alias. */
