@@ -139,6 +139,21 @@ _SIGS = [
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGS]
 
+# introspection entry points outside include/cnf.h (csrc/cnf_debug.cpp): host only, nothing is launched
+_I = C.POINTER(C.c_int)
+_DEBUG_SIGS = [
+    # the training backward's batch partitions, from the host functions the launch code calls
+    ('cnf_debug_train_convs', C.c_int, [_P, C.c_int, _I, C.c_int]),
+    ('cnf_debug_wgrad_choice', C.c_int, [_P] + [C.c_int] * 8 + [_I, C.c_int]),
+    ('cnf_debug_tconv_choice', C.c_int, [_P] + [C.c_int] * 11 + [_I, C.c_int]),
+    ('cnf_debug_lnb_slicing', C.c_int, [C.c_longlong, C.c_int, _I, C.c_int]),
+    ('cnf_debug_grad_rows_trips', C.c_int, [C.c_int]),
+    # the forward's k_pw launch shapes (a host-only dry run) and the images a workgroup of one loops over
+    ('cnf_debug_pw_shapes', C.c_int, [_P, C.c_int, _I, C.c_int]),
+    ('cnf_debug_pw_words', C.c_int, []),
+    ('cnf_debug_pw_ipw', C.c_int, [C.c_int] * 4),
+]
+
 _lib = None
 
 
@@ -163,7 +178,7 @@ def load(path: os.PathLike | str | None = None):
     except ImportError:   # a caller without torch: the system runtime is the only one
         pass
     lib = C.CDLL(str(p))
-    for name, res, args in _SIGS:
+    for name, res, args in _SIGS + _DEBUG_SIGS:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

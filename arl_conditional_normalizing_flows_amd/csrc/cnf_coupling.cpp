@@ -94,6 +94,10 @@ static int images_per_wg(int64_t units, int64_t slots, [[maybe_unused]] const ch
     return ipw;
 }
 
+int pw_images_per_wg(int tiles, int nprob, int B, bool res) {
+    return images_per_wg((int64_t)tiles * nprob * B, 512, res ? "CNF_PW_IPW_RES" : "CNF_PW_IPW");
+}
+
 // ----------------------------------------------------------------------------------------------
 // launch recording
 // ----------------------------------------------------------------------------------------------
@@ -337,7 +341,7 @@ static int pw_launch(Exec& E, int role, ConvLaunch& cl, const std::vector<ProbSp
     const bool lnf = probs[0].ln.slab.part != nullptr, resf = probs[0].res != nullptr, tapf = x.tap != nullptr;
     const int tiles = pw_tiles(a.H, a.W);
     a.tiles_per_img = tiles;
-    a.ipw = images_per_wg((int64_t)tiles * a.nprob * E.B, 512, resf ? "CNF_PW_IPW_RES" : "CNF_PW_IPW");
+    a.ipw = pw_images_per_wg(tiles, a.nprob, E.B, resf);
     const int grid_x = tiles * ((E.B + a.ipw - 1) / a.ipw), ilds = (int)cl.lds;
     if (x.tap) {
         a.umask = x.tap->mask;

@@ -134,6 +134,114 @@ int cnf_debug_t1_layout(const cnf_plan* plan, int coupling, int* words, int cap)
                         c->t1_map, words, cap);
 }
 
+// ---- the training backward's batch partitions (tests/test_batch_partitions.py) ---------------------------------
+// Each answer comes from the host function the launch code itself calls (wgrad_choice and the wgrad_*_split
+// shape functions, tconv_choice, lnb_slicing, grad_rows_trips); nothing is launched. plan: its debug options
+// (TRAIN_ALT) decide as they do in a call; null: the defaults.
+
+// The convolutions of coupling `coupling`'s multi-kernel backward (StreamedBwd) as words: [lds_bwd (the layer runs
+// the fused k_lds_bwd + k_grad_rows instead), hc, wc, dc1, dc2, nk, gc, R, n, then n x TRAINCONV_WORDS: role
+// (0 conv_out, 1 conv_b, 2 a grouped branch, 3 conv_a, 4 conv_in; residual blocks share their shapes), taps, dil,
+// cin, cout, then the input window's (floats per pixel, channel offset) and the output window's]. The weight
+// gradient reads X in the input window and dY in the output window; the data gradient maps cout channels of the
+// output window to cin channels of a tensor laid out as the input window.
+enum { TRAINCONV_WORDS = 9 };
+int cnf_debug_train_convs(const cnf_plan* plan, int coupling, int* words, int cap) {
+    const Coupling* c = coupling_of(plan, coupling);
+    if (!c || !words) return -1;
+    const NetParams& np = c->net[0];
+    std::vector<int> w{c->lds_bwd ? 1 : 0, c->hc, c->wc, c->dc1, c->dc2, c->nk, c->gc, c->R, 0};
+    auto conv = [&](int role, int taps, int dil, int cin, int cout, int x_cs, int x_off, int y_cs, int y_off) {
+        for (int v : {role, taps, dil, cin, cout, x_cs, x_off, y_cs, y_off}) w.push_back(v);
+        w[8]++;
+    };
+    conv(0, np.co.taps, 1, c->nk, c->dc2, c->nk, 0, c->dc2, 0);
+    if (c->R > 0) {
+        const RBParams& rb = np.rb[0];
+        conv(1, rb.cb.taps, 1, c->gc, c->nk, c->gc, 0, c->nk, 0);
+        for (size_t bi = 0; bi < c->br.size(); bi++) {
+            const Branch& b = c->br[bi];
+            conv(2, rb.gc[bi].taps, b.dil, b.cin, b.cout, c->nk, b.cin_off, c->gc, b.out_off);
+        }
+        conv(3, rb.ca.taps, 1, c->nk, c->nk, c->nk, 0, c->nk, 0);
+    }
+    conv(4, np.ci.taps, 1, c->dc1, c->nk, c->dc1, 0, c->nk, 0);
+    if ((int)w.size() > cap) return -1;
+    std::memcpy(words, w.data(), w.size() * sizeof(int));
+    return (int)w.size();
+}
+
+// The weight-gradient kernel of a taps-tap convolution cin -> cout (dilation dil, X in a tensor of x_cs floats per
+// pixel) on h x w images at batch B: [kernel (WGradKernel: 0 k_wgrad, 1 k_wgrad_thin, 2 k_wgrad_direct,
+// 3 k_wgrad_band), chunks (partial rows), units, per_chunk, short_last (WGradSplit; for k_wgrad: units = chunks,
+// per_chunk = chunk_px pixels of the flattened (image, pixel) axis, short_last = some chunk edge lies inside an
+// image), passes of k_grad_scatter's chunk loop]
+int cnf_debug_wgrad_choice(const cnf_plan* plan, int h, int w, int taps, int dil, int cin, int cout, int x_cs, int B,
+                           int* words, int cap) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!words || cap < 6 || h < 1 || w < 1 || cin < 1 || cout < 1 || B < 1) return -1;
+    const WGradChoice k = wgrad_choice(B, h, w, taps, dil, cin, cout, x_cs, true);
+    WGradSplit s{k.chunks, k.chunks, k.chunk_px, 0};
+    if (k.kernel == WGRAD_THIN) s = wgrad_thin_split(B, h, w);
+    if (k.kernel == WGRAD_DIRECT) s = wgrad_direct_split(B, h);
+    if (k.kernel == WGRAD_BAND) s = wgrad_band_split(B, h, w, taps, cin, cout);
+    if (k.kernel == WGRAD_VALU)
+        for (long long e = k.chunk_px; e < (long long)B * h * w; e += k.chunk_px)
+            if (e % (h * w) != 0) s.short_last = 1;
+    if (s.chunks != k.chunks) return -1;   // (the launchers throw on the same mismatch)
+    const int out[6] = {k.kernel, s.chunks, s.units, s.per_chunk, s.short_last, grad_scatter_trips(s.chunks)};
+    std::memcpy(words, out, sizeof(out));
+    return 6;
+}
+
+// The kernel of a data gradient (cout channels of a tensor with in_cs floats per pixel at channel in_off -> cin
+// channels at out_off of one with out_cs; 16-byte aligned buffers, as the train workspace's are) on h x w images at
+// batch B: [kernel (TConvKernel: 0 k_tconv, 1 k_tconv_thin, 2 k_tconv_band, 3 k_tconv_mfma), NR, SUB, TH,
+// all_taps, row bands per image]
+int cnf_debug_tconv_choice(const cnf_plan* plan, int h, int w, int taps, int dil, int cin, int cout, int in_cs,
+                           int in_off, int out_cs, int out_off, int B, int* words, int cap) {
+    OptScope os_(plan ? &plan->p->opts : nullptr);
+    if (!words || cap < 6 || h < 1 || w < 1 || cin < 1 || cout < 1 || B < 1) return -1;
+    TConvArgs a{};
+    a.in_cs = in_cs;
+    a.in_off = in_off;
+    a.K = cout;
+    a.out = reinterpret_cast<float*>(uintptr_t{256});   // (never dereferenced: its alignment alone is read)
+    a.out_cs = out_cs;
+    a.out_off = out_off;
+    a.N = cin;
+    a.H = h;
+    a.W = w;
+    a.taps = taps;
+    a.dil = dil;
+    a.sgn = -1;
+    a.B = B;
+    const TConvChoice c = tconv_choice(a);
+    const bool rows = c.kernel == TCONV_THIN || c.kernel == TCONV_BAND;
+    const int out[6] = {c.kernel, c.nr, c.sub, c.th, c.all_taps, rows ? (h + c.th - 1) / c.th : 0};
+    std::memcpy(words, out, sizeof(out));
+    return 6;
+}
+
+// launch_ln_backward's slicing of a B-image batch of n-element images: [S, bs, shared (1) or per-thread (0) sums,
+// reduction partials per image of its own k_lnb_reduce]
+int cnf_debug_lnb_slicing(long long n, int B, int* words, int cap) {
+    if (!words || cap < 4 || n < 1 || B < 1) return -1;
+    const LnbSlicing s = lnb_slicing(n, B);
+    const int out[4] = {s.S, s.bs, s.shared, s.rsl};
+    std::memcpy(words, out, sizeof(out));
+    return 4;
+}
+
+// images per workgroup of a k_pw launch with the tiles_per_img, nprob and res of one of cnf_debug_pw_shapes' shapes
+int cnf_debug_pw_ipw(int tiles_per_img, int nprob, int res, int B) {
+    if (tiles_per_img < 1 || nprob < 1 || B < 1) return -1;
+    return pw_images_per_wg(tiles_per_img, nprob, B, res != 0);
+}
+
+// passes of k_grad_rows' image loop at batch B
+int cnf_debug_grad_rows_trips(int B) { return B < 1 ? -1 : grad_rows_trips(B); }
+
 // diagnostic builds: the phase stamps the kernels of the last stamped launch left
 int cnf_debug_read_stamps(long long* out, int n) { return read_stamps(out, n); }
 int cnf_debug_read_bwd_stamps(long long* out, int n) { return read_bwd_stamps(out, n); }

@@ -671,6 +671,15 @@ struct TConvArgs {
 // reduction, the caller runs k_lnb_reduce)
 int launch_tconv(const TConvArgs& a, hipStream_t st);
 constexpr int LNR_MAXPARTS = 64;   // per image, k_tconv_* fused LN reductions
+// the kernel launch_tconv runs for a convolution and its tiling (launch_tconv launches what this returns;
+// cnf_debug_tconv_choice reports it). kernel TCONV_THIN: th = TR rows per workgroup; TCONV_BAND:
+// k_tconv_band<nr, sub> on bands of th rows; TCONV_MFMA: k_tconv_mfma<nr, vec>; TCONV_VALU: k_tconv<tn>
+enum TConvKernel { TCONV_VALU = 0, TCONV_THIN = 1, TCONV_BAND = 2, TCONV_MFMA = 3 };
+struct TConvChoice {
+    int kernel, nr, sub, th, all_taps, vec, tn;
+    size_t lds;
+};
+TConvChoice tconv_choice(const TConvArgs& a);
 
 // weight gradient: part[chunk][(tap*CI + ci)*CO + co] = sum over the chunk's pixels of
 // X[b, p + dil*off(tap), ci] * dY[b, p, co] (X with LN-on-load as in TConvArgs); bpart[chunk][co]
@@ -708,8 +717,21 @@ int wgrad_direct_chunks(int B, int H);
 bool wgrad_thin_ok(int H, int W, int taps, int dil, int CI, int CO);
 int wgrad_thin_chunks(int B, int H, int W);
 void launch_wgrad_thin(const WGradArgs& a, hipStream_t st);
+// How a weight-gradient launch partitions the batch, from the shape functions the launchers call (read
+// by cnf_debug_wgrad_choice). chunks: partial rows written. k_wgrad_direct: units = row bands per image,
+// per_chunk = RB rows per band, short_last = the image's last band has fewer than RB rows. k_wgrad_thin:
+// units = row tiles per image, per_chunk = ipw images per workgroup, short_last = the last image group
+// has fewer than ipw images. k_wgrad_band: units = (image, band of per_chunk = RB rows) work units, which
+// the `chunks` grid columns loop over once units > chunks; short_last as for k_wgrad_direct.
+struct WGradSplit {
+    int chunks, units, per_chunk, short_last;
+};
+WGradSplit wgrad_direct_split(int B, int H);
+WGradSplit wgrad_thin_split(int B, int H, int W);
+WGradSplit wgrad_band_split(int B, int H, int W, int taps, int CI, int CO);
 // dparams[map[i]] += sum_c part[c][i] for i < n (map[i] >= 0)
 void launch_grad_scatter(const float* part, int chunks, long long n, const int64_t* map, float* dparams, hipStream_t st);
+int grad_scatter_trips(int chunks);   // passes of k_grad_scatter's chunk loop (one up to 256 chunks)
 void launch_ln_stats(const float* x, long long n, int B, int act, float* stats, hipStream_t st);
 // LN + LeakyReLU backward: dx (=|+=) d/dx of LN(LeakyReLU(x)) given dxo = dL/d(LN output);
 // dgamma/dbeta (+=) per element; stats == null: LeakyReLU backward only
@@ -725,6 +747,13 @@ void launch_ln_backward(const float* x, const float* dxo, const float* gamma, co
                         long long n, int B, int act, float* dx, int accumulate, float* dgamma, float* dbeta,
                         float* scratch, hipStream_t st, int presum = 0, int pstride = 0,
                         unsigned long long cmask = 0, int cmod = 0);
+// launch_ln_backward's partition of a B-image batch of n-element images: rsl reduction partials per image
+// at stride rstride, S batch slices (k_lnb_apply's grid.y) of bs images (the last ones short or empty),
+// shared = a full slice's per-image sums go through LDS (bs <= 256) rather than per thread
+struct LnbSlicing {
+    int rsl, rstride, S, bs, shared;
+};
+LnbSlicing lnb_slicing(long long n, int B, int presum = 0, int pstride = 0);
 // Fused training backward of a k_net_lds layer (cnf_ldsbwd.hip): grid (B, 2 nets), one workgroup per
 // (image, net). Offsets table per net (int32, `offs_per_net` entries): canonical parameter offsets
 // (LN gamma / beta, the net's first parameter, tanh scale or -1) and dense backward-image offsets
@@ -772,6 +801,17 @@ int read_bwd_stamps(long long* host, int n);   // [0] = count, [1..] = s_memtime
 // dparams[lo_n + i] += sum_b part[n][b][i] (i < len_n, n = 0, 1; row floats per (net, image) row)
 void launch_grad_rows(const float* part, int B, int row, int64_t lo0, int64_t lo1, int len0, int len1, float* dparams,
                       hipStream_t st);
+int grad_rows_trips(int B);   // passes of k_grad_rows' image loop (one up to B = 64)
+
+// The weight-gradient kernel of a convolution on h x w images in a batch of B (cnf_train.cpp; wgrad_launch
+// launches what this returns, cnf_debug_wgrad_choice reports it). x_cs: floats per pixel of the tensor the
+// input window lies in; bias_follows: the dense image keeps the bias right after the weights.
+// WGRAD_VALU: k_wgrad, `chunks` runs of chunk_px pixels of the flattened (image, pixel) axis.
+enum WGradKernel { WGRAD_VALU = 0, WGRAD_THIN = 1, WGRAD_DIRECT = 2, WGRAD_BAND = 3 };
+struct WGradChoice {
+    int kernel, chunks, chunk_px;
+};
+WGradChoice wgrad_choice(int B, int h, int w, int taps, int dil, int cin, int cout, int x_cs, bool bias_follows);
 
 struct CoupBwArgs {
     const float* u;           // layer input [B][H][W][D]

@@ -864,8 +864,11 @@ void launch_lds_bwd(const LdsBwdArgs& a, int B, hipStream_t st) {
 // dst[net][i] += sum over images b of part[net][b][i], i < row; lo[net]: the net's first canonical
 // parameter. 32 elements per workgroup, 8 image slices per element (slice s: images s, s + 8, ...,
 // all of them in flight at once up to B = 64), fp64 sums, then a fixed-order LDS sum over the
-// slices: deterministic
+// slices: deterministic. Beyond B = 64 a slice takes further passes of 8 loads (images s + 64, ...; the
+// last pass ragged), added to the same fp64 sum in image order: grad_rows_trips passes (tested at B = 85
+// and 257, tests/test_batch_partitions.py)
 constexpr int GR_EL = 32, GR_SL = 8, GR_U = 8;
+int grad_rows_trips(int B) { return ((B > 1 ? B : 1) + GR_SL * GR_U - 1) / (GR_SL * GR_U); }
 __global__ __launch_bounds__(GR_EL * GR_SL) void k_grad_rows(const float* __restrict__ part, int B, int row, int64_t lo0,
                                                              int64_t lo1, int len0, int len1, float* __restrict__ dparams) {
     __shared__ double red[GR_SL][GR_EL];

@@ -474,6 +474,9 @@ struct CouplingOpts {
 // per-image sum of s in either direction, written by whichever kernel applies the law.
 void run_coupling(Exec& E, const Coupling& c, const float* u, float* v, double* ld_part, int dir,
                   const CouplingOpts& o = CouplingOpts{});
+// images a k_pw workgroup loops over: `tiles` 64-pixel tiles per image, nprob problems, B images (res: the
+// launch adds a residual); what the launch builder calls, reported by cnf_debug_pw_ipw
+int pw_images_per_wg(int tiles, int nprob, int B, bool res);
 
 }  // namespace cnf
 

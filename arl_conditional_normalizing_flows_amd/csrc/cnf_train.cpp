@@ -42,6 +42,19 @@ int wgrad_chunks(int B, int npx) {
 
 }  // namespace
 
+WGradChoice wgrad_choice(int B, int h, int w, int taps, int dil, int cin, int cout, int x_cs, bool bias_follows) {
+    if (train_valu_kernels() || !wgrad_band_ok(h, w, taps, dil, cin, cout)) {
+        const int chunks = wgrad_chunks(B, h * w);
+        const long long total = (long long)B * h * w;
+        return {WGRAD_VALU, chunks, (int)(((total + chunks - 1) / chunks + 15) / 16 * 16)};
+    }
+    if ((long long)h * w * x_cs * 4 < (1LL << 31) && wgrad_thin_ok(h, w, taps, dil, cin, cout) && bias_follows)
+        return {WGRAD_THIN, wgrad_thin_chunks(B, h, w), 0};
+    if ((opts().train_alt & ALT_WGRAD_BAND) == 0 && wgrad_direct_ok(h, w, taps))
+        return {WGRAD_DIRECT, wgrad_direct_chunks(B, h), -1};
+    return {WGRAD_BAND, wgrad_band_chunks(B, h, w, taps, cin, cout), 0};
+}
+
 void ldsbwd_geom(const Coupling& c, LdsBwdArgs& a) {
     const int HW = c.hc * c.wc;
     a.row = (int)std::max(c.net[0].hi - c.net[0].lo, c.net[1].hi - c.net[1].lo);
@@ -424,34 +437,29 @@ WGradArgs wgrad_args(const TExec& E, Geom g, Src x, const LnIn& ln, Src dy, cons
 // dW, db of a conv on stream st: the kernel its shape allows, then the scatter of its partial rows
 // through the dense map onto the canonical parameters
 void wgrad_launch(const TExec& E, WGradArgs a, const PackedConv& pc, hipStream_t st) {
-    const int h = a.H, w = a.W, cin = a.CI, cout = a.CO;
+    const int cin = a.CI, cout = a.CO;
     const int64_t* map = E.p.dev_bw_map;
     const long long nw = (long long)pc.taps * cin * cout;
-    if (train_valu_kernels() || !wgrad_band_ok(h, w, pc.taps, a.dil, cin, cout)) {
-        a.chunks = wgrad_chunks(E.B, h * w);
-        const long long total = (long long)E.B * h * w;
-        a.chunk_px = (int)(((total + a.chunks - 1) / a.chunks + 15) / 16 * 16);
+    const WGradChoice k = wgrad_choice(E.B, a.H, a.W, pc.taps, a.dil, cin, cout, a.x_cs, pc.db == pc.dw + nw);
+    a.chunks = k.chunks;
+    if (k.kernel == WGRAD_VALU) {
+        a.chunk_px = k.chunk_px;
         launch_wgrad(a, st);
         launch_grad_scatter(a.part, a.chunks, nw, map + pc.dw, E.dparams, st);
         launch_grad_scatter(a.bpart, a.chunks, cout, map + pc.db, E.dparams, st);
         return;
     }
     // thin outputs (the streamed conv_out, CO = dc2): k_wgrad_thin, rows of [weights | bias] as below
-    if ((long long)h * w * a.x_cs * 4 < (1LL << 31) && wgrad_thin_ok(h, w, pc.taps, a.dil, cin, cout) &&
-        pc.db == pc.dw + nw) {
-        a.chunks = wgrad_thin_chunks(E.B, h, w);
+    if (k.kernel == WGRAD_THIN) {
         launch_wgrad_thin(a, st);
         launch_grad_scatter(a.part, a.chunks, nw + cout, map + pc.dw, E.dparams, st);
         return;
     }
     // k_wgrad_direct (ALT_WGRAD_BAND: k_wgrad_band): rows of [weights | bias]; the dense image keeps the
     // bias right after the weights (pc.db == pc.dw + taps * cin * cout), so one scatter reduces both
-    if ((opts().train_alt & ALT_WGRAD_BAND) == 0 && wgrad_direct_ok(h, w, pc.taps)) {
-        a.chunks = wgrad_direct_chunks(E.B, h);
-        a.chunk_px = -1;
+    if (k.kernel == WGRAD_DIRECT) {
+        a.chunk_px = k.chunk_px;
         a.zero = E.zeros();
-    } else {
-        a.chunks = wgrad_band_chunks(E.B, h, w, pc.taps, cin, cout);
     }
     launch_wgrad(a, st);
     if (pc.db != pc.dw + nw) throw std::logic_error("dense image: bias not after the weights");

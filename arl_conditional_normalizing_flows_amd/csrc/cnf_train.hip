@@ -691,14 +691,9 @@ static bool tconv_thin_on() { return (opts().train_alt & ALT_NO_THIN) == 0; }
 static bool train_valu() { return (opts().train_alt & ALT_VALU) != 0; }
 bool train_valu_kernels() { return train_valu(); }
 
-int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
-    TConvArgs a = a_in;
-    const int npx = a.H * a.W;
-    // a fused LN reduction writes one partial per workgroup of an image: drop it where there are too many
-    auto lnr_ok = [&](const dim3& g) {
-        if (a.lnr_part != nullptr && a.lnr_base + (int)(g.x * g.z) > a.lnr_stride) a.lnr_part = nullptr;
-        return a.lnr_part != nullptr ? (int)(g.x * g.z) : 0;
-    };
+// launch_tconv's choice: the first kernel, in the order below, whose conditions the convolution meets
+TConvChoice tconv_choice(const TConvArgs& a) {
+    TConvChoice c{};
     const bool band_off = (opts().train_alt & ALT_NO_TCONV_BAND) != 0;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (!train_valu() && tconv_thin_on() && a.taps == 9 && a.dil == 1 && a.K >= 1 && a.K <= 4 &&
@@ -708,16 +703,10 @@ int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
         const int PS = 256 / (a.N / 4);
         const int TR = std::max(1, std::min(a.H, PS * 4 / a.W));
         if (TR * a.W <= PS * 4) {
-            const dim3 g((a.H + TR - 1) / TR, a.B, 1), blk(256);
-            const int np = lnr_ok(g);
-            const size_t lds = (((size_t)(TR + 2) * (a.W + 2) * a.K + 3) / 4 * 4 + (size_t)9 * a.K * a.N) * 4;
-            switch (a.K) {
-                case 1: hipLaunchKernelGGL((k_tconv_thin<1>), g, blk, lds, st, a, TR); break;
-                case 2: hipLaunchKernelGGL((k_tconv_thin<2>), g, blk, lds, st, a, TR); break;
-                case 3: hipLaunchKernelGGL((k_tconv_thin<3>), g, blk, lds, st, a, TR); break;
-                default: hipLaunchKernelGGL((k_tconv_thin<4>), g, blk, lds, st, a, TR); break;
-            }
-            return np;
+            c.kernel = TCONV_THIN;
+            c.th = TR;
+            c.lds = (((size_t)(TR + 2) * (a.W + 2) * a.K + 3) / 4 * 4 + (size_t)9 * a.K * a.N) * 4;
+            return c;
         }
     }
     if (!train_valu() && !band_off && a.taps == 9 && a.dil <= 2 && a.W <= 64 && a.W >= 1) {
@@ -746,23 +735,13 @@ int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
         const int all_taps = (long long)(band + 9 * w1) <= at_lim * 1024 ? 1 : 0;
         const size_t lds = band + (all_taps ? 9 : 1) * w1;
         if (lds <= 160 * 1024) {
-            const dim3 g((a.H + TH - 1) / TH, a.B, (a.N + NS - 1) / NS), blk(256);
-            const int np = lnr_ok(g);
-            if (sub == 4)
-                hipLaunchKernelGGL((k_tconv_band<1, 4>), g, blk, lds, st, a, TH, all_taps);
-            else if (sub == 2 && nr == 1)
-                hipLaunchKernelGGL((k_tconv_band<1, 2>), g, blk, lds, st, a, TH, all_taps);
-            else if (sub == 2)
-                hipLaunchKernelGGL((k_tconv_band<2, 2>), g, blk, lds, st, a, TH, all_taps);
-            else if (nr == 1)
-                hipLaunchKernelGGL((k_tconv_band<1, 1>), g, blk, lds, st, a, TH, all_taps);
-            else if (nr == 2)
-                hipLaunchKernelGGL((k_tconv_band<2, 1>), g, blk, lds, st, a, TH, all_taps);
-            else if (nr == 3)
-                hipLaunchKernelGGL((k_tconv_band<3, 1>), g, blk, lds, st, a, TH, all_taps);
-            else
-                hipLaunchKernelGGL((k_tconv_band<4, 1>), g, blk, lds, st, a, TH, all_taps);
-            return np;
+            c.kernel = TCONV_BAND;
+            c.nr = nr;
+            c.sub = sub;
+            c.th = TH;
+            c.all_taps = all_taps;
+            c.lds = lds;
+            return c;
         }
     }
     if (!train_valu()) {
@@ -772,11 +751,67 @@ int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
         const size_t lds1 = (size_t)G * 16 * NS * 4;
         if (lds1 <= 64 * 1024) {
             // every tap's weights in LDS at once when they fit (no per-tap barriers), else per tap
-            const int all_taps = lds1 * a.taps <= 64 * 1024 ? 1 : 0;
-            const size_t lds = all_taps ? lds1 * a.taps : lds1;
-            const bool vec = a.K % 4 == 0 && a.in_cs % 4 == 0 && a.in_off % 4 == 0;
-            const dim3 g((npx + 63) / 64, a.B, (a.N + NS - 1) / NS), blk(256);
-            const int np = lnr_ok(g);
+            c.kernel = TCONV_MFMA;
+            c.nr = nr;
+            c.all_taps = lds1 * a.taps <= 64 * 1024 ? 1 : 0;
+            c.lds = c.all_taps ? lds1 * a.taps : lds1;
+            c.vec = a.K % 4 == 0 && a.in_cs % 4 == 0 && a.in_off % 4 == 0 ? 1 : 0;
+            return c;
+        }
+    }
+    c.kernel = TCONV_VALU;
+    c.tn = a.N <= 4 ? 4 : a.N <= 16 ? 16 : 64;
+    return c;
+}
+
+int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
+    TConvArgs a = a_in;
+    const int npx = a.H * a.W;
+    // a fused LN reduction writes one partial per workgroup of an image: drop it where there are too many
+    auto lnr_ok = [&](const dim3& g) {
+        if (a.lnr_part != nullptr && a.lnr_base + (int)(g.x * g.z) > a.lnr_stride) a.lnr_part = nullptr;
+        return a.lnr_part != nullptr ? (int)(g.x * g.z) : 0;
+    };
+    const TConvChoice c = tconv_choice(a);
+    if (c.kernel == TCONV_THIN) {
+        const int TR = c.th;
+        const dim3 g((a.H + TR - 1) / TR, a.B, 1), blk(256);
+        const int np = lnr_ok(g);
+        switch (a.K) {
+            case 1: hipLaunchKernelGGL((k_tconv_thin<1>), g, blk, c.lds, st, a, TR); break;
+            case 2: hipLaunchKernelGGL((k_tconv_thin<2>), g, blk, c.lds, st, a, TR); break;
+            case 3: hipLaunchKernelGGL((k_tconv_thin<3>), g, blk, c.lds, st, a, TR); break;
+            default: hipLaunchKernelGGL((k_tconv_thin<4>), g, blk, c.lds, st, a, TR); break;
+        }
+        return np;
+    }
+    if (c.kernel == TCONV_BAND) {
+        const int nr = c.nr, sub = c.sub, TH = c.th, all_taps = c.all_taps, NS = 16 * nr;
+        const size_t lds = c.lds;
+        const dim3 g((a.H + TH - 1) / TH, a.B, (a.N + NS - 1) / NS), blk(256);
+        const int np = lnr_ok(g);
+        if (sub == 4)
+            hipLaunchKernelGGL((k_tconv_band<1, 4>), g, blk, lds, st, a, TH, all_taps);
+        else if (sub == 2 && nr == 1)
+            hipLaunchKernelGGL((k_tconv_band<1, 2>), g, blk, lds, st, a, TH, all_taps);
+        else if (sub == 2)
+            hipLaunchKernelGGL((k_tconv_band<2, 2>), g, blk, lds, st, a, TH, all_taps);
+        else if (nr == 1)
+            hipLaunchKernelGGL((k_tconv_band<1, 1>), g, blk, lds, st, a, TH, all_taps);
+        else if (nr == 2)
+            hipLaunchKernelGGL((k_tconv_band<2, 1>), g, blk, lds, st, a, TH, all_taps);
+        else if (nr == 3)
+            hipLaunchKernelGGL((k_tconv_band<3, 1>), g, blk, lds, st, a, TH, all_taps);
+        else
+            hipLaunchKernelGGL((k_tconv_band<4, 1>), g, blk, lds, st, a, TH, all_taps);
+        return np;
+    }
+    if (c.kernel == TCONV_MFMA) {
+        const int nr = c.nr, NS = 16 * nr, all_taps = c.all_taps;
+        const size_t lds = c.lds;
+        const bool vec = c.vec != 0;
+        const dim3 g((npx + 63) / 64, a.B, (a.N + NS - 1) / NS), blk(256);
+        const int np = lnr_ok(g);
 #define CNF_TM(NR_)                                                                                   \
     if (nr == NR_) {                                                                                  \
         if (vec)                                                                                      \
@@ -785,11 +820,10 @@ int launch_tconv(const TConvArgs& a_in, hipStream_t st) {
             hipLaunchKernelGGL((k_tconv_mfma<NR_, false>), g, blk, lds, st, a, all_taps);           \
         return np;                                                                                    \
     }
-            CNF_TM(1) CNF_TM(2) CNF_TM(3) CNF_TM(4)
+        CNF_TM(1) CNF_TM(2) CNF_TM(3) CNF_TM(4)
 #undef CNF_TM
-        }
     }
-    const int TN = a.N <= 4 ? 4 : a.N <= 16 ? 16 : 64;
+    const int TN = c.tn;
     const int TP = 4096 / TN;
     const dim3 g((npx + TP - 1) / TP, a.B, (a.N + TN - 1) / TN), blk(256);
     if (TN == 4)
@@ -1303,6 +1337,19 @@ int wgrad_direct_chunks(int B, int H) {
     return B * nb;
 }
 
+WGradSplit wgrad_direct_split(int B, int H) {
+    WGradArgs a{};
+    a.B = B;
+    a.H = H;
+    a.W = 4;
+    a.taps = 1;
+    a.CI = 1;
+    a.CO = 1;
+    int RB, nb, mt, nt, gy, gz;
+    wgrad_direct_shape(a, RB, nb, mt, nt, gy, gz);
+    return {wgrad_direct_chunks(B, H), nb, RB, H % RB != 0 ? 1 : 0};
+}
+
 static void launch_wgrad_direct(const WGradArgs& a, hipStream_t st) {
     int RB, nbands, mt, nt, gy, gz;
     wgrad_direct_shape(a, RB, nbands, mt, nt, gy, gz);
@@ -1452,6 +1499,12 @@ int wgrad_thin_chunks(int B, int H, int W) {
     return ntile * ((B + ipw - 1) / ipw);
 }
 
+WGradSplit wgrad_thin_split(int B, int H, int W) {
+    int TR, ipw, ntile;
+    wgrad_thin_shape(B, H, W, TR, ipw, ntile);
+    return {wgrad_thin_chunks(B, H, W), ntile, ipw, B % ipw != 0 ? 1 : 0};
+}
+
 void launch_wgrad_thin(const WGradArgs& a, hipStream_t st) {
     int TR, ipw, ntile;
     wgrad_thin_shape(a.B, a.H, a.W, TR, ipw, ntile);
@@ -1487,6 +1540,16 @@ int wgrad_band_chunks(int B, int H, int W, int taps, int CI, int CO) {
     if (c > WGRAD_MAX_CHUNKS) c = WGRAD_MAX_CHUNKS;
     if (c > nunits) c = nunits;
     return c < 1 ? 1 : c;
+}
+
+WGradSplit wgrad_band_split(int B, int H, int W, int taps, int CI, int CO) {
+    WGradArgs a{};
+    a.B = B;
+    a.H = H;
+    a.W = W;
+    int RB, nunits;
+    wgrad_units(a, RB, nunits);
+    return {wgrad_band_chunks(B, H, W, taps, CI, CO), nunits, RB, H % RB != 0 ? 1 : 0};
 }
 
 size_t wgrad_band_lds(int H, int W, int taps, int dil, int CI, int CO) {
@@ -1532,8 +1595,12 @@ void launch_wgrad(const WGradArgs& a, hipStream_t st) {
 
 // 32 elements per workgroup (one 128-byte line of a partial row per half-wave), 32 slices of the
 // chunk rows per element, every load of a slice in flight at once (<= 8 per thread up to 256 chunks),
-// then a fixed-order LDS sum over the slices: deterministic
+// then a fixed-order LDS sum over the slices: deterministic. Beyond 256 chunks (k_wgrad_direct writes one
+// row per image once B > WGRAD_MAX_CHUNKS) a slice takes further passes of 8 loads, chunks sl + 256, ...,
+// added to the same fp64 sum in chunk order: grad_scatter_trips passes (tested at 257 chunks,
+// tests/test_batch_partitions.py)
 constexpr int GS_EL = 32, GS_SL = 32, GS_U = 8;
+int grad_scatter_trips(int chunks) { return (std::max(chunks, 1) + GS_SL * GS_U - 1) / (GS_SL * GS_U); }
 __global__ __launch_bounds__(GS_EL * GS_SL) void k_grad_scatter(const float* __restrict__ part, int chunks, long long n,
                                                                 const int64_t* __restrict__ map, float* __restrict__ dparams) {
     __shared__ double red[GS_SL][GS_EL];
@@ -1702,6 +1769,10 @@ __global__ __launch_bounds__(LNT) void k_lnb_reduce(const float* __restrict__ x,
 // at a time, their loads in flight together): dx, and the slice's dgamma / dbeta partials summed in
 // registers; k_lnb_gsum adds the slices in a fixed order (no atomics: deterministic)
 constexpr int LNA_MAXIMG = 256;   // images per batch slice whose sums k_lnb_apply shares through LDS
+// images per batch slice of S slices over B images (the last slices short or empty), and whether a slice of
+// nimg images shares its per-image sums through LDS (else every thread sums them): B > 8 * 256
+__host__ __device__ constexpr int lnb_slice_images(int B, int S) { return (B + S - 1) / S; }
+__host__ __device__ constexpr bool lnb_shared_sums(int nimg) { return nimg <= LNA_MAXIMG; }
 __global__ __launch_bounds__(256) void k_lnb_apply(const float* __restrict__ x, const float* __restrict__ dxo,
                                                    const float* __restrict__ gamma, const float* __restrict__ stats,
                                                    const double* __restrict__ sums, int rsl, int rstride, long long n,
@@ -1710,12 +1781,12 @@ __global__ __launch_bounds__(256) void k_lnb_apply(const float* __restrict__ x, 
                                                    float* __restrict__ bpart, unsigned long long cmask, int cmod) {
     const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     const int S = gridDim.y, sl = blockIdx.y;
-    const int bs = (B + S - 1) / S, b_lo = sl * bs, b_hi = min(B, b_lo + bs);
+    const int bs = lnb_slice_images(B, S), b_lo = sl * bs, b_hi = min(B, b_lo + bs);
     const float inv_n0 = 1.f / (float)n;
     // the slice's per-image means of g and g * xhat, summed once per workgroup (one thread per image, its
     // partials in order) instead of by every thread
     __shared__ float smg[LNA_MAXIMG], smgh[LNA_MAXIMG];
-    const bool shared_sums = stats != nullptr && b_hi - b_lo <= LNA_MAXIMG;
+    const bool shared_sums = stats != nullptr && lnb_shared_sums(b_hi - b_lo);
     if (shared_sums) {
         const int b = b_lo + (int)threadIdx.x;
         if (b < b_hi) {
@@ -1826,23 +1897,33 @@ __global__ __launch_bounds__(256) void k_lnb_gsum(const float* __restrict__ gpar
     dbeta[e] += b;
 }
 
-void launch_ln_backward(const float* x, const float* dxo, const float* gamma, const float* stats, double* sums,
-                        long long n, int B, int act, float* dx, int accumulate, float* dgamma, float* dbeta,
-                        float* scratch, hipStream_t st, int presum, int pstride, unsigned long long cmask, int cmod) {
-    if (cmod < 0 || cmod > 64) throw std::invalid_argument("launch_ln_backward: channel mask over <= 64 channels");
+LnbSlicing lnb_slicing(long long n, int B, int presum, int pstride) {
     // slices per image: at least two full passes of the workgroup each (64 images x 8 slices fill the
     // GPU where one workgroup per image used a quarter of it)
 #ifndef CNF_LNB_RS
 #define CNF_LNB_RS LNB_RS
 #endif
-    int rsl = (int)std::min<long long>(CNF_LNB_RS, std::max<long long>(1, (n / 4) / (2LL * LNT)));
-    int rstride = rsl;
+    LnbSlicing s{};
+    s.rsl = (int)std::min<long long>(CNF_LNB_RS, std::max<long long>(1, (n / 4) / (2LL * LNT)));
+    s.rstride = s.rsl;
     if (presum > 0) {
-        rsl = presum;
-        rstride = pstride > 0 ? pstride : presum;
-    } else if (stats)
+        s.rsl = presum;
+        s.rstride = pstride > 0 ? pstride : presum;
+    }
+    s.S = B < LNB_SLICES ? B : LNB_SLICES;
+    s.bs = lnb_slice_images(B, s.S);
+    s.shared = lnb_shared_sums(std::min(B, s.bs)) ? 1 : 0;
+    return s;
+}
+
+void launch_ln_backward(const float* x, const float* dxo, const float* gamma, const float* stats, double* sums,
+                        long long n, int B, int act, float* dx, int accumulate, float* dgamma, float* dbeta,
+                        float* scratch, hipStream_t st, int presum, int pstride, unsigned long long cmask, int cmod) {
+    if (cmod < 0 || cmod > 64) throw std::invalid_argument("launch_ln_backward: channel mask over <= 64 channels");
+    const LnbSlicing sl = lnb_slicing(n, B, presum, pstride);
+    const int rsl = sl.rsl, rstride = sl.rstride, S = sl.S;
+    if (presum <= 0 && stats)
         hipLaunchKernelGGL(k_lnb_reduce, dim3(B, rsl), dim3(LNT), 0, st, x, dxo, gamma, stats, n, sums, cmask, cmod);
-    const int S = B < LNB_SLICES ? B : LNB_SLICES;
     float* gpart = scratch;
     float* bpart = scratch + (size_t)LNB_SLICES * n;
     hipLaunchKernelGGL(k_lnb_apply, dim3((unsigned)((n + 1023) / 1024), S), dim3(256), 0, st, x, dxo, gamma, stats,

@@ -191,11 +191,12 @@ def test_gradients_match_oracle(gpu, name, B, extra):
     check_gradients(gpu, kw, xy, options, f'{name} {extra}', perturb)
 
 
-def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None, params=None):
+def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None, params=None, got=None):
     """The HIP gradient of the flow cFlow(**kw) at xy (weights params, by default init_params(5)) and its 4
     loss terms against float64 autograd, under the module docstring's bar. perturb: None (no perturbation
     term) or (eps list, seeds per eps). refs: (G_ref, terms_ref, G32) of this kw, xy and params when the
-    caller has them already."""
+    caller has them already. got: (param_specs, gradient, loss terms) of a flow.gradients(xy) call the
+    caller made on such a flow (then none is made here)."""
     B = xy.shape[0]
     ora = OracleCFlow(**kw)
     P = ora.init_params(5) if params is None else params
@@ -214,8 +215,12 @@ def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None
                 Gp, _ = oracle_grads(kw, P, np.asarray(xy, np.float64) * (1.0 + eps * rng.standard_normal(xy.shape)))
                 for k in G_spread:
                     G_spread[k] = np.maximum(G_spread[k], np.abs(Gp[k].reshape(-1) - G_ref[k].reshape(-1)))
-    flow = _gpu_flow(kw, P, gpu, options)
-    g, terms = flow.gradients(torch.from_numpy(xy).to(gpu))
+    if got is None:
+        flow = _gpu_flow(kw, P, gpu, options)
+        g, terms = flow.gradients(torch.from_numpy(xy).to(gpu))
+        param_specs = flow.param_specs
+    else:
+        param_specs, g, terms = got
     g = g.cpu().numpy().astype(np.float64)
     terms = [float(t) for t in terms]
     # the north-star bound of the forward parity tests (test_gpu_parity.test_nll_matches_oracle): 1e-5 of
@@ -230,7 +235,7 @@ def check_gradients(gpu, kw, xy, options=None, label='', perturb=None, refs=None
     gmax = max(float(np.max(np.abs(v))) for v in G_ref.values())
     worst = (0.0, '')
     bad = []
-    for n, o, s in flow.param_specs:
+    for n, o, s in param_specs:
         size = int(np.prod(s)) if s else 1
         ref = np.asarray(G_ref[n], np.float64).reshape(-1)
         got = g[o:o + size]
