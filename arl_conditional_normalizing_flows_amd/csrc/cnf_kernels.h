@@ -635,6 +635,57 @@ struct SampleQuantileArgs {
 };
 void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st);
 
+// ---- density of given images (cnf_logprob.hip, cnf_flow_log_prob) ---------------------------------
+// One chunk of the N pairs of a log_prob call: pairs g0 .. g0 + n - 1, pair g = (image, condition) =
+// (g / K, g % K) pairwise (K >= 1), (g, g) paired (K == 0); its xy / zy live in the chunk buffers at g - g0.
+struct LogpChunk {
+    long long g0;        // first pair of the chunk
+    int n, K;            // pairs in the chunk; conditions (0: paired)
+    int HW, D, x_d;      // io shape
+};
+// The one reduction rule of these kernels: a thread folds its elements in fp64 in element order (which
+// elements it owns depends on the image shape alone), the wave sums by the fixed xor butterfly (wave_sum),
+// the waves of a workgroup are added in wave order and a pair's partial slots in slot order. A pair's value
+// therefore does not depend on chunk, B, K or the pair's place in its chunk.
+// k_logp_gather's tile: LOGP_QUADS quads of 4 consecutive pixels per workgroup, one per thread; an image of
+// HW pixels has logp_parts(HW) tiles and as many log_jac partial slots
+constexpr int LOGP_QUADS = 256;
+inline int logp_parts(int HW) { return (HW + 4 * LOGP_QUADS - 1) / (4 * LOGP_QUADS); }
+// k_logp_gather: xy[i] = concat(v, y[cond]) for the chunk's pairs, v = logit_value(x[img] - y[cond]) (the
+// subtraction with residual, the map with logit: sample_post_value's inverse), and the pair's log_jac
+// partials lj[i][part] = sum over the tile's x elements of -log(e (1 - e)), e = a + c1 x' in fp32 as the map
+// sees it (0 without logit). An element with e outside (0, 1) (NaN included) adds -inf and enters xy as 0, so
+// the flow runs on finite values.
+struct LogpGatherArgs {
+    const float* x;      // [B][HW][x_d]
+    const float* y;      // [K or B][HW][D - x_d]
+    float* xy;           // [n][HW][D]
+    double* lj;          // [n][logp_parts(HW)]
+    int logit, residual;
+    LogitK lk;
+};
+void launch_logp_gather(const LogpChunk& c, const LogpGatherArgs& a, hipStream_t st);
+// k_logp_finish: per pair of the chunk, one workgroup and one pass over zy[i]: q = sum z^2 over the x
+// channels, dev = sum |y_hat - y[cond]| over the others; llz = -0.5 q - 0.5 HW x_d log(2 pi), J = the pair's
+// lj slots in order + lj_const (HW x_d (log c1 - log span) with logit, else 0), log_prob =
+// (float)(llz + ld[i] + J). J == -inf (an element outside the map's domain): log_prob = -inf, log_jac = -inf,
+// llz, logdet and y_dev NaN. Outputs indexed by the pair g0 + i, each may be null. No counter, no atomics.
+struct LogpFinishArgs {
+    const float* zy;     // [n][HW][D]
+    const float* y;
+    const float* ld;     // [n] the forward's per-image log-det
+    const double* lj;    // [n][parts]
+    double lj_const;
+    float *log_prob, *llz, *logdet, *log_jac, *y_dev;
+};
+void launch_logp_finish(const LogpChunk& c, const LogpFinishArgs& a, hipStream_t st);
+// k_logp_posterior: per row b of log_prob [B][K], a_k = log_prob[b][k] + log_prior[k] (null: + 0) in fp64,
+// m = max_k a_k, lse = m + log(sum_k exp(a_k - m)); posterior[b][k] = (float)exp(a_k - lse), log_evidence[b]
+// = (float)lse (each may be null). A row of -inf only: posterior NaN, log_evidence -inf. One wave per row
+// for K <= 64, else one workgroup.
+void launch_logp_posterior(const float* log_prob, const float* log_prior, float* posterior, float* log_evidence,
+                           int B, int K, hipStream_t st);
+
 
 // ---- training (cnf_train.hip) -------------------------------------------------------------------
 // Generic fp32 convolution for the training path over the dense backward image (taps x k x n):

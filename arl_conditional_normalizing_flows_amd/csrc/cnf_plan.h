@@ -391,9 +391,11 @@ void ensure_tables(Plan& p);
 // nz (cnf_flow_forward_noise): xy is the caller's buffer for the noisy input, which the first coupling's
 // k_net_lds writes while gathering from nz->src with the noise applied (a k_noise pass into it first when
 // that layer is streamed)
+// append: keep the launches recorded so far (cnf_flow_log_prob records one forward per chunk), as
+// InverseOpts::append does for the inverse
 void flow_forward(Plan& p, const float* params, const float* aux, const float* xy, float* zy,
                   float* logdet_per_image, void* workspace, int B, hipStream_t stream, bool save_inputs,
-                  const InputPrepArgs* nz = nullptr);
+                  const InputPrepArgs* nz = nullptr, bool append = false);
 struct InverseOpts {
     // keep the launches recorded so far (cnf_flow_sample records one inverse per chunk)
     bool append = false;

@@ -44,9 +44,9 @@ bool defers(const Plan& p, const Coupling& c, int li, int step) {
 
 void flow_forward(Plan& p, const float* params, const float* aux, const float* xy, float* zy,
                   float* logdet_per_image, void* workspace, int B, hipStream_t stream, bool save_inputs,
-                  const InputPrepArgs* nz) {
+                  const InputPrepArgs* nz, bool append) {
     if (!p.dry) ensure_tables(p);
-    p.recorded.clear();
+    if (!append) p.recorded.clear();
     Exec E{p, params, aux, (char*)workspace, p.layout(B), B, stream};
     TrainLayout TL;
     if (save_inputs) TL = p.train_layout(B);

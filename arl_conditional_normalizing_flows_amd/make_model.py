@@ -687,6 +687,86 @@ class cFlow:
             ptr(out.get('hist')), ptr(out.get('quantiles')), ptr(ws), B, _stream()), 'cnf_flow_sample_score')
         return out
 
+    # -- density of given images ----------------------------------------------------------------
+    def log_prob(self, x, y, logit_a=None, residual=False, chunk=None, pairwise=None, return_terms=False,
+                 log_prior=None, return_posterior=False):
+        """The model's log-density of given images, per condition: sample()'s counterpart, in one native call
+        (cnf_flow_log_prob).
+
+        x: [B,H,W,x_d] on the device (or [H,W,x_d] for one image), in the space of sample()'s 'samples': after
+        de_logitify(., logit_a) when logit_a is given and after + y when residual. y: [B,H,W,D-x_d], image b
+        under its own condition (paired), or with pairwise=True [K,H,W,D-x_d], every image under every condition
+        ([H,W,D-x_d]: one condition). pairwise=None means paired when the leading dimensions agree and raises
+        otherwise. The pairs run through the forward `chunk` at a time (default min(pairs, 64)); no result
+        depends on chunk, bit for bit, and the pairwise call equals the paired one on the expanded pairs.
+
+        Returns a dict, every entry [B] (paired) or [B,K] (pairwise):
+        'log_prob' = llz + logdet + log_jac, the log-density of x given y in the space x lives in (sample()'s
+        'log_prob' is the same quantity before de_logitify / the residual: it lacks log_jac);
+        'bits_per_dim' = -log_prob / (H W x_d ln 2);
+        with return_terms 'llz' and 'logdet' (what nll_sums reports for the flow-space image of x), 'log_jac'
+        (the log-Jacobian of the logit map over the image; 0 without logit_a) and 'y_dev' (sum |y_hat - y|);
+        with return_posterior (pairwise only) 'posterior' [B,K] = softmax_k(log_prob + log_prior), log_prior [K]
+        or None for a uniform prior, and 'log_evidence' [B], the row's log-sum-exp.
+        An image with an element outside the logit map's domain has log_prob -inf (and NaN llz, logdet,
+        y_dev) under every condition; the other images are untouched."""
+        x, y = _as_input(x, 'x'), _as_input(y, 'y')
+        H, W, D = self.io_shape
+        x_d = self.x_d
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if y.dim() == 3:
+            y = y.unsqueeze(0)
+        if tuple(x.shape[1:]) != (H, W, x_d):
+            raise ValueError(f'x has shape {tuple(x.shape)}, expected [None, {H}, {W}, {x_d}]')
+        if tuple(y.shape[1:]) != (H, W, D - x_d):
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {H}, {W}, {D - x_d}]')
+        B = int(x.shape[0])
+        if pairwise is None:
+            if int(y.shape[0]) != B:
+                raise ValueError(f'x holds {B} images and y {int(y.shape[0])} conditions: pass pairwise=True to '
+                                 f'score every image under every condition')
+            pairwise = False
+        if not pairwise and int(y.shape[0]) != B:
+            raise ValueError(f'paired mode needs one condition per image: x holds {B}, y {int(y.shape[0])}')
+        K = int(y.shape[0]) if pairwise else 0
+        N = B * K if pairwise else B
+        shape = (B, K) if pairwise else (B,)
+        if (return_posterior or log_prior is not None) and not pairwise:
+            raise AssertionError('cFlow.log_prob: the posterior over conditions needs pairwise=True')
+        if log_prior is not None:
+            return_posterior = True
+            log_prior = _as_input(torch.as_tensor(log_prior, dtype=torch.float32, device=x.device), 'log_prior')
+            if tuple(log_prior.shape) != (K,):
+                raise ValueError(f'log_prior has shape {tuple(log_prior.shape)}, expected [{K}]')
+        if chunk is None:
+            chunk = max(1, min(N, 64))
+        desc = _lib.cnf_logp_desc(K, int(chunk), float(logit_a or 0.0), int(bool(residual)))
+        lib = _lib.load()
+        key = ('log_prob', int(chunk))
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(lib.cnf_plan_logp_workspace_bytes(self._plan, B, C.byref(desc)))
+            if nbytes <= 0:   # an argument error, as the reference's asserts
+                raise AssertionError(f'cFlow.log_prob: {lib.cnf_last_error().decode()}')
+            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+
+        def new(*s):
+            return torch.empty(s, device=x.device, dtype=torch.float32)
+        out = {'log_prob': new(*shape)}
+        if return_terms:
+            for n in ('llz', 'logdet', 'log_jac', 'y_dev'):
+                out[n] = new(*shape)
+        if return_posterior:
+            out['posterior'], out['log_evidence'] = new(B, K), new(B)
+        check(lib.cnf_flow_log_prob(self._plan, ptr(self.params), ptr(self._aux), ptr(x), ptr(y), C.byref(desc),
+                                    ptr(out['log_prob']), ptr(out.get('llz')), ptr(out.get('logdet')),
+                                    ptr(out.get('log_jac')), ptr(out.get('y_dev')), ptr(log_prior),
+                                    ptr(out.get('posterior')), ptr(out.get('log_evidence')), ptr(ws), B, _stream()),
+              'cnf_flow_log_prob')
+        out['bits_per_dim'] = out['log_prob'] * (-1.0 / (H * W * x_d * math.log(2.0)))
+        return out
+
     # -- loss -----------------------------------------------------------------------------------
     def nll_sums(self, xy, zy=None, logdet_per_image=None):
         """Per-batch sums of the NLL terms on device: (sum loss_i, sum -llz_i, sum -lly_i,

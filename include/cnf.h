@@ -271,6 +271,56 @@ int cnf_flow_sample_score(cnf_plan* plan, const float* params, const float* aux,
                           float* log_prob, int* rank, float* abs_err, float* sq_err, int* hist,
                           float* quantiles, void* workspace, int B, void* stream);
 
+/* The density of given images: the counterpart of cnf_flow_sample. x[B][H][W][x_d] lives in the space
+ * of the returned samples (after de_logitify and the residual); every image is scored against its own
+ * condition (paired) or against each of K conditions (pairwise), N = B or B*K pairs, pair i =
+ * (image, condition) = (i / K, i % K). For pair i, with v the flow-space image of x:
+ *   v        = logit(x - y): the input y is subtracted if residual, then cnf_logit's forward map is
+ *              applied if logit_a -- the exact inverse of cnf_flow_sample's post-transforms, in the
+ *              kernels' own fp32 expressions; xy = concat(v, y), every y channel unchanged
+ *   llz, logdet  as cnf_nll reports them for (xy, zy = cnf_flow_forward(xy))
+ *   y_dev    = sum_{h,w,c} |y_hat - y|, unweighted, as cnf_flow_sample's
+ *   log_jac  = sum over the image's x elements of log|dv/dx|: 0 without logit_a (the residual shift has
+ *              unit Jacobian); with it each element adds log c1 - log e - log(1 - e) - log span,
+ *              e = a + c1 x' (x' = x - y if residual), c1 = (1 - a) b = 1 - 2a, span = logit(1 - a) -
+ *              logit(a), in fp64 from the fp32 e the map itself uses
+ *   log_prob = llz + logdet + log_jac: cnf_flow_sample_logp's log_prob moved into the sample space
+ * An image with an element outside the map's domain (e not in (0, 1), NaN included) has density 0 under
+ * every such pair: log_prob = log_jac = -inf, and llz, logdet, y_dev are NaN (the flow ran on 0 in that
+ * element's place, so nothing non-finite enters it or reaches another pair).
+ * posterior[b][k] = softmax_k(log_prob[b][k] + log_prior[k]) (log_prior NULL: uniform, + 0) and
+ * log_evidence[b] = that row's log-sum-exp, both in fp64 from the fp32 log_prob, max-shifted; a row whose
+ * entries are all -inf gives a NaN posterior and -inf evidence.
+ * The pairs run through the forward `chunk` at a time: per chunk a gather (xy and the log_jac partials),
+ * cnf_flow_forward's launches, and one finishing pass over zy; then, if asked for, the posterior. Every
+ * sum is taken in a fixed order that depends on the image shape alone, so no result depends on chunk, B,
+ * K, the pair's place in its chunk, the stream or the workspace's earlier contents, bit for bit, and the
+ * pairwise call equals the paired call on the B*K expanded pairs. */
+typedef struct cnf_logp_desc {
+    int   num_conditions; /* K >= 1: y is [K][H][W][D-x_d], every image against every condition,
+                             outputs [B][K]; 0: paired, y is [B][H][W][D-x_d], outputs [B] */
+    int   chunk;          /* pairs per forward, >= 1; results do not depend on it */
+    float logit_a;        /* 0: none; in (0,0.5): x is in de_logitify(., a)'s output space */
+    int   residual;       /* 1: x is x_flow + y; needs io_d - x_d == x_d */
+} cnf_logp_desc;
+
+/* Workspace bytes of cnf_flow_log_prob: cnf_plan_workspace_bytes(desc->chunk), one chunk each of xy, zy,
+ * the per-image log-det and the log_jac partials; independent of B and of num_conditions. 0, with the
+ * reason in cnf_last_error, for a NULL or invalid argument. */
+size_t cnf_plan_logp_workspace_bytes(const cnf_plan* plan, int B, const cnf_logp_desc* desc);
+
+/* Outputs log_prob, llz, logdet, log_jac, y_dev: [N] each, any may be NULL; posterior [B][K] and
+ * log_evidence [B] (pairwise only; they read log_prob, which must then be given); log_prior [K] or NULL.
+ * CNF_E_INVALID before any HIP call for: a NULL plan, params, aux, workspace, x or y; B < 1; no output
+ * requested; num_conditions < 0; chunk < 1; logit_a outside {0} u (0, 0.5); residual with D - x_d != x_d;
+ * posterior or log_evidence in paired mode or without log_prob; log_prior without posterior or
+ * log_evidence. The launches are recorded under their own names (k_logp_gather, the forward's,
+ * k_logp_finish per chunk, k_logp_posterior) for the measurement hooks below. */
+int cnf_flow_log_prob(cnf_plan* plan, const float* params, const float* aux, const float* x,
+                      const float* y, const cnf_logp_desc* desc, float* log_prob, float* llz,
+                      float* logdet, float* log_jac, float* y_dev, const float* log_prior,
+                      float* posterior, float* log_evidence, void* workspace, int B, void* stream);
+
 /* coupling_layer.forward_and_Jacobian (:1258-1328) for layer `layer` of
  * layers_list: u -> v (shape of the layer's in_shape); logdet_accum[B] +=
  * per-image sum of A(u1) (pass NULL to skip). u and v must not alias. */
