@@ -51,6 +51,12 @@ class cnf_sample_score_desc(C.Structure):
                 ('quantiles', C.c_float * 8)]
 
 
+class cnf_cascade_desc(C.Structure):
+    _fields_ = [('num_stages', C.c_int), ('num_samples', C.c_int * 4), ('chunk', C.c_int),
+                ('temperature', C.c_float * 4), ('seed', C.c_uint64), ('offset', C.c_uint64 * 4),
+                ('logit_a', C.c_float), ('residual', C.c_int)]
+
+
 class cnf_logp_desc(C.Structure):
     _fields_ = [('num_conditions', C.c_int), ('chunk', C.c_int), ('logit_a', C.c_float), ('residual', C.c_int)]
 
@@ -93,6 +99,10 @@ _SIGS = [
                                        _P]),
     ('cnf_flow_sample_score', C.c_int, [_P, _F, _F, _F, C.POINTER(cnf_sample_desc), C.POINTER(cnf_sample_score_desc),
                                         _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_cascade_workspace_bytes', C.c_size_t, [C.POINTER(_P), C.c_int, C.POINTER(cnf_cascade_desc)]),
+    ('cnf_flow_sample_cascade', C.c_int, [C.POINTER(_P), C.POINTER(_F), C.POINTER(_F), _F, C.POINTER(cnf_cascade_desc),
+                                          C.POINTER(cnf_sample_score_desc), _F, _F, _F, _F, _F, _F, _F, C.POINTER(_F),
+                                          C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, C.c_int, _P]),
     ('cnf_plan_logp_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_logp_desc)]),
     ('cnf_flow_log_prob', C.c_int, [_P, _F, _F, _F, _F, C.POINTER(cnf_logp_desc), _F, _F, _F, _F, _F, _F, _F, _F, _P,
                                     C.c_int, _P]),

@@ -582,11 +582,15 @@ struct SampleFoldArgs {
     float* std;
     int B, logit, residual;
     LogitK lk;
+    const float* zy;      // non-null (cascade): the condition of image i is the y channels of zy[i], not y[b]
 };
 void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream_t st);
 // k_sample_ydev: y_dev[g0 + i] = sum_{p, c >= x_d} |xy_hat[i, p, c] - y[(g0 + i) / S, p, c - x_d]|, one
 // wave per image, fp64 lane sums in element order then a fixed-order wave sum
 void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st);
+// k_sample_ydev_node: the same against the image's own condition, the y channels of the chunk's zy (which the
+// inverse leaves intact)
+void launch_sample_ydev_node(const SampleChunk& c, const float* xy_hat, const float* zy, float* y_dev, hipStream_t st);
 // k_sample_logp: log_prob[g0 + i] = (float)(-0.5 q - 0.5 n log(2 pi) + L), n = HW * x_d, q the fp64 sum of
 // z^2 over image i's latent (channels < x_d of the chunk's zy), L the fp64 sum of image i's log-det slots
 // ld_part[nl][c.n][np] as the chunk's inverse wrote them (k_ld_reduce's order); one wave per image
@@ -609,6 +613,7 @@ struct SampleScoreArgs {
     int logit, residual, bins;
     float lo, scale;     // scale = (float)bins / (hi - lo)
     LogitK lk;
+    const float* zy;      // as SampleFoldArgs::zy
 };
 constexpr int SCORE_MAX_BINS = 256, SCORE_MAX_QUANTILES = 8;
 void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStream_t st);
@@ -621,6 +626,7 @@ struct SampleSqerrArgs {
     float* sq_err;        // [B][S]
     int logit, residual;
     LogitK lk;
+    const float* zy;      // as SampleFoldArgs::zy
 };
 void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st);
 // k_sample_quantiles, once after the last chunk, one thread per element: quantiles[j][b][p][c] of level q[j] from
@@ -634,6 +640,40 @@ struct SampleQuantileArgs {
     float q[SCORE_MAX_QUANTILES];
 };
 void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st);
+
+// ---- cascaded sampling (cnf_sample.hip, cnf_flow_sample_cascade) --------------------------------
+// The kernels above with a non-null zy (k_sample_fold_node, k_sample_score_node, k_sample_sqerr_node) and
+// k_sample_ydev_node take each image's condition from the y channels of its own zy: at stage >= 2 of a
+// cascade a node's condition is `up` of its parent's value, not y[b]. Same arithmetic, same bits.
+// k_child_latent: one chunk c of a child stage's zy from the parent stage's chunk buffers. Child node g has
+// parent g / Sc, image g / Sc - pg0 of the parent chunk. Per child pixel (h, w): the x channels get
+// temperature * N(0,1) by k_latent's rule; y channel cy gets the parent's value at pixel (h / 2, w / 2):
+// sample_post_value(parent xy_hat[.., cy], logit, residual, parent zy[.., x_d + cy]) -- the post-transform,
+// cnf_up and k_latent in one pass, the parent's image never written at full size. D == 2 x_d.
+struct ChildLatentArgs {
+    const float* pxy;     // the parent chunk's xy_hat [pn][HW / 4][D]
+    const float* pzy;     // the parent chunk's zy (its y channels: the parent's own condition)
+    float* zy;            // the child chunk's zy [n][HW][D]
+    long long pg0;        // first node of the parent chunk
+    int Sc, W;            // children per parent; the child's width
+    float temperature;
+    unsigned long long seed, offset;
+    int logit, residual;
+    LogitK lk;
+};
+void launch_child_latent(const SampleChunk& c, const ChildLatentArgs& a, hipStream_t st);
+// k_block_dev: block_dev[g0 + i] = (float) sum over the 2x2 pixel blocks and channels c < x_d of
+// |0.25 * sum over the block's 4 pixels in row-major order of ((double)v - (double)y)|, v the image's sample value,
+// y its condition (the y channels of zy[i]; D == 2 x_d, H and W even). One wave per image, fp64 lane sums over
+// (block, c) in element order, then the fixed-order wave sum.
+struct BlockDevArgs {
+    const float* xy_hat;
+    const float* zy;
+    float* block_dev;     // [B][S]
+    int W, logit, residual;
+    LogitK lk;
+};
+void launch_block_dev(const SampleChunk& c, const BlockDevArgs& a, hipStream_t st);
 
 // ---- density of given images (cnf_logprob.hip, cnf_flow_log_prob) ---------------------------------
 // One chunk of the N pairs of a log_prob call: pairs g0 .. g0 + n - 1, pair g = (image, condition) =

@@ -8,6 +8,11 @@
 //   k_sample_score      the draws against a truth per element: rank, mean |error|, histogram (cnf_flow_sample_score)
 //   k_sample_sqerr      per image sum (sample - truth)^2
 //   k_sample_quantiles  per element quantiles from the finished histogram
+//   k_child_latent      one chunk of a cascade's child stage: `up` of the parent chunk's sample values on the y
+//                       channels, k_latent's normals on the x channels (cnf_flow_sample_cascade)
+//   k_block_dev         per image sum over 2x2 pixel blocks of |block mean of (sample - condition)|
+// k_sample_fold, k_sample_ydev, k_sample_score and k_sample_sqerr are templates on where an image's condition
+// comes from: y[b] (cnf_flow_sample) or the y channels of its own zy (the cascade's nodes).
 // All HBM-bound element / reduction kernels; no global atomics (k_sample_score counts with integer LDS adds
 // inside the tile its workgroup owns), every floating-point sum in a fixed order.
 #include <hip/hip_runtime.h>
@@ -61,6 +66,9 @@ constexpr int FOLD_E = 32, FOLD_L = 8, FOLD_BATCH = 64;
 // serial chain per element, three operations a draw, which thread (e, 0) runs over the batch in draw order.
 // The draws s0 .. s1 - 1 of b in the chunk are the same for the whole workgroup: the barriers sit in
 // uniform control flow.
+// NODE (cnf_flow_sample_cascade, a.zy non-null): the residual's y is the draw's own condition, the y channel
+// of its image of the chunk's zy, loaded next to the value; everything else, the arithmetic included, is the same.
+template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldArgs a, long long b0, int bpc) {
     __shared__ float sh[FOLD_BATCH][FOLD_E];
     const int per = q.HW * q.x_d;   // elements per condition
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldAr
     const size_t se = (size_t)b * per + pc;
     const bool stats = a.state != nullptr;
     const bool folds = stats && valid && l == 0;
-    const float yv = a.residual && valid ? a.y[se] : 0.f;   // (D - x_d == x_d: y[b] has x's shape)
+    const float yv = !NODE && a.residual && valid ? a.y[se] : 0.f;   // (D - x_d == x_d: y[b] has x's shape)
     float K = 0.f, S1 = 0.f, S2 = 0.f;
     if (folds && s0 > 0) {
         K = a.state[se];
@@ -85,17 +93,19 @@ __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldAr
     }
     const size_t img = (size_t)q.HW * q.D;
     const float* __restrict__ src = a.xy_hat + (size_t)p * q.D + c;   // the element in image 0 of the chunk
+    const float* __restrict__ ysrc = NODE ? a.zy + (size_t)p * q.D + q.x_d + c : nullptr;   // its condition
     for (int sb = s0; sb < s1; sb += FOLD_BATCH) {
-        float w[FOLD_BATCH / FOLD_L];
+        float w[FOLD_BATCH / FOLD_L], yw[NODE ? FOLD_BATCH / FOLD_L : 1];
 #pragma unroll
         for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
             const int s = sb + l + j * FOLD_L;
             w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
+            if constexpr (NODE) yw[j] = a.residual && valid && s < s1 ? ysrc[(size_t)(gb + s - q.g0) * img] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
             const int s = sb + l + j * FOLD_L;
-            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, yv);
+            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, NODE ? yw[j] : yv);
             if (valid && s < s1 && a.samples != nullptr) a.samples[(size_t)(gb + s) * per + pc] = v;
             if (stats) sh[l + j * FOLD_L][e] = v;
         }
@@ -122,6 +132,8 @@ __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldAr
 }
 
 // one wave per image of the chunk; lane sums in fp64 over its elements in order, then the wave sum
+// NODE: y is the chunk's zy, and image i's condition its y channels
+template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, const float* __restrict__ xy_hat,
                                                      const float* __restrict__ y, float* __restrict__ y_dev) {
     const int lane = threadIdx.x & 63;
@@ -131,11 +143,12 @@ __global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, const float*
     const long long b = g / q.S;
     const int yd = q.D - q.x_d, n = q.HW * yd;
     const float* __restrict__ xi = xy_hat + (size_t)i * q.HW * q.D;
-    const float* __restrict__ yb = y + (size_t)b * n;
+    const float* __restrict__ yb = NODE ? y + (size_t)i * q.HW * q.D : y + (size_t)b * n;
     double s = 0.0;
     for (int e = lane; e < n; e += 64) {
         const int p = e / yd, c = e - p * yd;
-        s += (double)fabsf(xi[(size_t)p * q.D + q.x_d + c] - yb[e]);
+        const float yv = NODE ? yb[(size_t)p * q.D + q.x_d + c] : yb[e];
+        s += (double)fabsf(xi[(size_t)p * q.D + q.x_d + c] - yv);
     }
     s = wave_sum(s);
     if (lane == 0) y_dev[g] = (float)s;
@@ -176,6 +189,8 @@ size_t score_lds_bytes(int bins) { return ((size_t)bins * SCORE_EP + FOLD_BATCH 
 // thread (e, 0) folds |v - truth| over the batch in draw order. The chunk's counts then go to the outputs,
 // which the workgroup owns: added to what the earlier chunks left there, or stored when the chunk holds
 // b's first draw. s0, s1 and the null tests are the same for the whole workgroup: the barriers are uniform.
+// NODE: as k_sample_fold's.
+template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScoreArgs a, long long b0, int bpc) {
     extern __shared__ __align__(16) int score_lds[];
     int* hs = score_lds;
@@ -194,7 +209,7 @@ __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScore
     const size_t se = (size_t)b * per + pc;
     const bool owner = valid && l == 0;
     const bool errs = a.abs_err != nullptr, hist = a.hist != nullptr;
-    const float yv = a.residual && valid ? a.y[se] : 0.f;
+    const float yv = !NODE && a.residual && valid ? a.y[se] : 0.f;
     const float tv = a.truth != nullptr && valid ? a.truth[se] : 0.f;
     float acc = errs && owner && !first ? a.abs_err[se] : 0.f;
     int below = 0;
@@ -204,17 +219,19 @@ __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScore
     }
     const size_t img = (size_t)q.HW * q.D;
     const float* __restrict__ src = a.xy_hat + (size_t)p * q.D + c;   // the element in image 0 of the chunk
+    const float* __restrict__ ysrc = NODE ? a.zy + (size_t)p * q.D + q.x_d + c : nullptr;   // its condition
     for (int sb = s0; sb < s1; sb += FOLD_BATCH) {
-        float w[FOLD_BATCH / FOLD_L];
+        float w[FOLD_BATCH / FOLD_L], yw[NODE ? FOLD_BATCH / FOLD_L : 1];
 #pragma unroll
         for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
             const int s = sb + l + j * FOLD_L;
             w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
+            if constexpr (NODE) yw[j] = a.residual && valid && s < s1 ? ysrc[(size_t)(gb + s - q.g0) * img] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
             const int s = sb + l + j * FOLD_L;
-            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, yv);
+            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, NODE ? yw[j] : yv);
             if (valid && s < s1) {
                 below += v < tv ? 1 : 0;
                 if (hist) {
@@ -258,7 +275,8 @@ __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScore
     }
 }
 
-// one wave per image of the chunk, as k_sample_ydev
+// one wave per image of the chunk, as k_sample_ydev; NODE: the residual's y from image i's zy
+template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_sqerr(SampleChunk q, SampleSqerrArgs a) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -268,11 +286,12 @@ __global__ __launch_bounds__(256) void k_sample_sqerr(SampleChunk q, SampleSqerr
     const int n = q.HW * q.x_d;
     const float* __restrict__ xi = a.xy_hat + (size_t)i * q.HW * q.D;
     const float* __restrict__ tb = a.truth + (size_t)b * n;
-    const float* __restrict__ yb = a.y + (size_t)b * n;   // (read with residual only: y[b] has x's shape)
+    // (read with residual only: y[b] has x's shape)
+    const float* __restrict__ yb = NODE ? a.zy + (size_t)i * q.HW * q.D : a.y + (size_t)b * n;
     double s = 0.0;
     for (int e = lane; e < n; e += 64) {
         const int p = e / q.x_d, c = e - p * q.x_d;
-        const float yv = a.residual ? yb[e] : 0.f;
+        const float yv = a.residual ? (NODE ? yb[(size_t)p * q.D + q.x_d + c] : yb[e]) : 0.f;
         const float v = sample_post_value(xi[(size_t)p * q.D + c], a.logit, a.lk, a.residual, yv);
         const double d = (double)v - (double)tb[e];
         s += d * d;
@@ -315,6 +334,73 @@ __global__ __launch_bounds__(256) void k_sample_quantiles(SampleQuantileArgs a) 
     }
 }
 
+// k_latent's threads and stores for one chunk of a child stage of a cascade. The x channels: k_latent's
+// normal. A y channel cy: the parent's sample value at pixel (h / 2, w / 2) -- sample_post_value of the parent
+// chunk's xy_hat with the parent's own condition (the y channels of the parent chunk's zy) -- i.e. cnf_up of the
+// value k_sample_fold would have stored for the parent, which is never written. D == 2 x_d.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_child_latent(SampleChunk q, ChildLatentArgs a) {
+    constexpr int V = VEC ? 4 : 1;
+    const int units = q.D / V;   // per pixel
+    const int pW = a.W / 2;
+    const size_t pimg = (size_t)(q.HW / 4) * q.D;   // a parent image
+    const long long n = (long long)q.n * q.HW * units;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const int cu = (int)(e % units);
+        const long long ip = e / units;   // (image of the chunk, pixel)
+        const int p = (int)(ip % q.HW);
+        const long long g = q.g0 + ip / q.HW;
+        const int h = p / a.W, w = p - h * a.W;
+        // the parent's image in its chunk (g / Sc >= pg0: the chunk holds children of that chunk's nodes only)
+        const size_t pe = (size_t)(g / a.Sc - a.pg0) * pimg + (size_t)((h / 2) * pW + w / 2) * q.D;
+        const uint64_t z0 = a.offset + ((uint64_t)g * q.HW + p) * q.x_d;
+        float v[V];
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            const int c = cu * V + j;
+            if (c < q.x_d) {
+                v[j] = a.temperature * instance_noise_value(0.f, false, 0.f, a.seed, z0 + c);
+            } else {
+                const int cy = c - q.x_d;
+                const float yv = a.residual ? a.pzy[pe + q.x_d + cy] : 0.f;
+                v[j] = sample_post_value(a.pxy[pe + cy], a.logit, a.lk, a.residual, yv);
+            }
+        }
+        if constexpr (VEC)
+            *reinterpret_cast<f4*>(a.zy + (size_t)e * 4) = f4{v[0], v[1], v[2], v[3]};
+        else
+            a.zy[e] = v[0];
+    }
+}
+
+// one wave per image of the chunk, as k_sample_ydev: lane sums in fp64 over the image's (2x2 block, channel)
+// elements in order, then the wave sum. An element: the four pixels of the block in row-major order, each
+// (double)v - (double)y (exact), added in that order, times 0.25 (exact), its absolute value.
+__global__ __launch_bounds__(256) void k_block_dev(SampleChunk q, BlockDevArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= q.n) return;   // (whole waves)
+    const int bw = a.W / 2, n = (q.HW / 4) * q.x_d;
+    const float* __restrict__ xi = a.xy_hat + (size_t)i * q.HW * q.D;
+    const float* __restrict__ zi = a.zy + (size_t)i * q.HW * q.D;
+    double s = 0.0;
+    for (int e = lane; e < n; e += 64) {
+        const int blk = e / q.x_d, c = e - blk * q.x_d;
+        const int bh = blk / bw, bx = blk - bh * bw;
+        double d = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const size_t o = (size_t)((2 * bh + (k >> 1)) * a.W + 2 * bx + (k & 1)) * q.D + c;
+            const float yv = zi[o + q.x_d];
+            const float v = sample_post_value(xi[o], a.logit, a.lk, a.residual, yv);
+            d += (double)v - (double)yv;
+        }
+        s += fabs(0.25 * d);
+    }
+    s = wave_sum(s);
+    if (lane == 0) a.block_dev[q.g0 + i] = (float)s;
+}
+
 int grid_for(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
@@ -339,11 +425,18 @@ void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream
     const long long b0 = c.g0 / c.S, b1 = (c.g0 + c.n - 1) / c.S;
     const int nb = (int)(b1 - b0 + 1);
     const int bpc = (c.HW * c.x_d + FOLD_E - 1) / FOLD_E;   // workgroups per condition
-    CNF_LAUNCH(k_sample_fold, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
+    if (a.zy != nullptr)
+        CNF_LAUNCH(k_sample_fold<true>, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
+    else
+        CNF_LAUNCH(k_sample_fold<false>, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
 }
 
 void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st) {
-    CNF_LAUNCH(k_sample_ydev, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, y, y_dev);
+    CNF_LAUNCH(k_sample_ydev<false>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, y, y_dev);
+}
+
+void launch_sample_ydev_node(const SampleChunk& c, const float* xy_hat, const float* zy, float* y_dev, hipStream_t st) {
+    CNF_LAUNCH(k_sample_ydev<true>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, zy, y_dev);
 }
 
 void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
@@ -355,15 +448,35 @@ void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStre
     const long long b0 = c.g0 / c.S, b1 = (c.g0 + c.n - 1) / c.S;
     const int nb = (int)(b1 - b0 + 1);
     const int bpc = (c.HW * c.x_d + FOLD_E - 1) / FOLD_E;   // workgroups per condition
-    CNF_LAUNCH(k_sample_score, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
+    if (a.zy != nullptr)
+        CNF_LAUNCH(k_sample_score<true>, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
+    else
+        CNF_LAUNCH(k_sample_score<false>, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
 }
 
 void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st) {
-    CNF_LAUNCH(k_sample_sqerr, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
+    if (a.zy != nullptr)
+        CNF_LAUNCH(k_sample_sqerr<true>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
+    else
+        CNF_LAUNCH(k_sample_sqerr<false>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
 }
 
 void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st) {
     CNF_LAUNCH(k_sample_quantiles, dim3(grid_for(a.n)), dim3(256), 0, st, a);
+}
+
+void launch_child_latent(const SampleChunk& c, const ChildLatentArgs& a, hipStream_t st) {
+    if (c.D % 4 == 0) {
+        const long long n = (long long)c.n * c.HW * (c.D / 4);
+        CNF_LAUNCH(k_child_latent<true>, dim3(grid_for(n)), dim3(256), 0, st, c, a);
+    } else {
+        const long long n = (long long)c.n * c.HW * c.D;
+        CNF_LAUNCH(k_child_latent<false>, dim3(grid_for(n)), dim3(256), 0, st, c, a);
+    }
+}
+
+void launch_block_dev(const SampleChunk& c, const BlockDevArgs& a, hipStream_t st) {
+    CNF_LAUNCH(k_block_dev, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
 }
 
 }  // namespace cnf

@@ -5,18 +5,12 @@
 #include <cstring>
 #include <string>
 
-#include "cnf_api.h"
-#include "cnf_plan.h"
+#include "cnf_sampling.h"
 
 using namespace cnf;
 
-namespace {
+namespace cnf {
 
-// the sample workspace: the inverse workspace of `chunk` images, one chunk of zy and of xy_hat, and the
-// statistics state (K, S1, S2) [3][B][H][W][x_d]
-struct SampleLayout {
-    size_t zy = 0, xy = 0, state = 0, total = 0;
-};
 SampleLayout sample_layout(const Plan& p, int B, int chunk) {
     const cnf_flow_desc& d = p.desc;
     const size_t n_uv = (size_t)d.io_h * d.io_w * d.io_d;
@@ -48,18 +42,6 @@ const char* sample_desc_error(const Plan& p, int B, const cnf_sample_desc* s) {
     return nullptr;
 }
 
-// the score arguments of cnf_flow_sample_score (every output null: cnf_flow_sample_logp)
-struct ScoreArgs {
-    const cnf_sample_score_desc* sd = nullptr;
-    const float* truth = nullptr;
-    int* rank = nullptr;
-    float* abs_err = nullptr;
-    float* sq_err = nullptr;
-    int* hist = nullptr;
-    float* quantiles = nullptr;
-    bool any() const { return rank || abs_err || sq_err || hist || quantiles; }
-};
-
 // the argument errors of the score part (no output given: none)
 const char* score_error(const ScoreArgs& sc) {
     if (!sc.any()) return nullptr;
@@ -81,6 +63,25 @@ const char* score_error(const ScoreArgs& sc) {
     }
     return nullptr;
 }
+
+// k_sample_quantiles' arguments for n elements, from the score descriptor
+SampleQuantileArgs quantile_args(const ScoreArgs& sc, long long n) {
+    SampleQuantileArgs ua;
+    std::memset(&ua, 0, sizeof(ua));
+    ua.hist = sc.hist;
+    ua.quantiles = sc.quantiles;
+    ua.n = n;
+    ua.bins = sc.sd->bins;
+    ua.nq = sc.sd->num_quantiles;
+    ua.lo = sc.sd->lo;
+    ua.hi = sc.sd->hi;
+    for (int j = 0; j < ua.nq; j++) ua.q[j] = sc.sd->quantiles[j];
+    return ua;
+}
+
+}  // namespace cnf
+
+namespace {
 
 // the body of cnf_flow_sample (log_prob null: its launches, exactly), cnf_flow_sample_logp and
 // cnf_flow_sample_score (every score output null: cnf_flow_sample_logp's launches, exactly)
@@ -178,16 +179,7 @@ int flow_sample(const char* who, cnf_plan* plan, const float* params, const floa
                      [=](void* st) { launch_sample_sqerr(c, qa, (hipStream_t)st); });
     }
     if (sc.quantiles != nullptr) {
-        SampleQuantileArgs ua;
-        std::memset(&ua, 0, sizeof(ua));
-        ua.hist = sc.hist;
-        ua.quantiles = sc.quantiles;
-        ua.n = (long long)B * per;
-        ua.bins = sc.sd->bins;
-        ua.nq = sc.sd->num_quantiles;
-        ua.lo = sc.sd->lo;
-        ua.hi = sc.sd->hi;
-        for (int j = 0; j < ua.nq; j++) ua.q[j] = sc.sd->quantiles[j];
+        const SampleQuantileArgs ua = quantile_args(sc, (long long)B * per);
         Exec E{p, params, aux, ws, p.layout(1), 1, (hipStream_t)stream};
         E.record("k_sample_quantiles", 0, 4.0 * (double)ua.n * (ua.bins + ua.nq),   // (the second walk hits the cache)
                  [=](void* st) { launch_sample_quantiles(ua, (hipStream_t)st); });

@@ -43,6 +43,44 @@ def _as_input(t, what='input'):
     return t.contiguous()
 
 
+def _score_setup(out, shape, S, device, truth, hist, quantiles, return_sq_err):
+    """The score arguments of sample(): checks truth [B,H,W,x_d] = shape, allocates the requested score outputs
+    into `out` for S draws per condition, and returns (cnf_sample_score_desc, truth)."""
+    B, H, W, x_d = shape
+    sd = _lib.cnf_sample_score_desc()
+    if truth is not None:
+        truth = _as_input(truth, 'truth')
+        if truth.dim() == 3:
+            truth = truth.unsqueeze(0)
+        if tuple(truth.shape) != (B, H, W, x_d):
+            raise ValueError(f'truth has shape {tuple(truth.shape)}, expected [{B}, {H}, {W}, {x_d}]')
+        out['rank'] = torch.empty((B, H, W, x_d), device=device, dtype=torch.int32)
+        out['abs_err'] = torch.empty((B, H, W, x_d), device=device, dtype=torch.float32)
+        if return_sq_err is None or return_sq_err:
+            out['sq_err'] = torch.empty((B, max(S, 0)), device=device, dtype=torch.float32)
+    elif return_sq_err:
+        raise AssertionError('cFlow.sample: return_sq_err needs truth')
+    if hist is not None:
+        bins, lo, hi = hist
+        sd.bins, sd.lo, sd.hi = int(bins), float(lo), float(hi)
+        if not 2 <= sd.bins <= 256:   # (before the allocation below is sized by it)
+            raise AssertionError(f'cFlow.sample: hist bins must be in 2..256, got {bins}')
+        out['hist'] = torch.empty((B, H, W, x_d, sd.bins), device=device, dtype=torch.int32)
+        k = torch.arange(sd.bins, device=device, dtype=torch.float32)
+        out['hist_centers'] = sd.lo + (k + 0.5) * ((sd.hi - sd.lo) / sd.bins)
+    if quantiles is not None:
+        if hist is None:
+            raise AssertionError('cFlow.sample: quantiles needs hist=(bins, lo, hi)')
+        levels = [float(q) for q in quantiles]
+        if not 1 <= len(levels) <= 8:
+            raise AssertionError(f'cFlow.sample: 1..8 quantile levels, got {len(levels)}')
+        sd.num_quantiles = len(levels)
+        for j, q in enumerate(levels):
+            sd.quantiles[j] = q
+        out['quantiles'] = torch.empty((len(levels), B, H, W, x_d), device=device, dtype=torch.float32)
+    return sd, truth
+
+
 # ---------------------------------------------------------------------------------------------
 # layers
 # ---------------------------------------------------------------------------------------------
@@ -648,38 +686,9 @@ class cFlow:
         """sample()'s call with a truth, a histogram box or quantile levels (cnf_flow_sample_score): adds the
         score outputs to `out`, the dict of the plain outputs already allocated."""
         H, W, D = self.io_shape
-        B, S, x_d = int(y.shape[0]), int(desc.num_samples), self.x_d
-        sd = _lib.cnf_sample_score_desc()
-        if truth is not None:
-            truth = _as_input(truth, 'truth')
-            if truth.dim() == 3:
-                truth = truth.unsqueeze(0)
-            if tuple(truth.shape) != (B, H, W, x_d):
-                raise ValueError(f'truth has shape {tuple(truth.shape)}, expected [{B}, {H}, {W}, {x_d}]')
-            out['rank'] = torch.empty((B, H, W, x_d), device=y.device, dtype=torch.int32)
-            out['abs_err'] = torch.empty((B, H, W, x_d), device=y.device, dtype=torch.float32)
-            if return_sq_err is None or return_sq_err:
-                out['sq_err'] = torch.empty((B, max(S, 0)), device=y.device, dtype=torch.float32)
-        elif return_sq_err:
-            raise AssertionError('cFlow.sample: return_sq_err needs truth')
-        if hist is not None:
-            bins, lo, hi = hist
-            sd.bins, sd.lo, sd.hi = int(bins), float(lo), float(hi)
-            if not 2 <= sd.bins <= 256:   # (before the allocation below is sized by it)
-                raise AssertionError(f'cFlow.sample: hist bins must be in 2..256, got {bins}')
-            out['hist'] = torch.empty((B, H, W, x_d, sd.bins), device=y.device, dtype=torch.int32)
-            k = torch.arange(sd.bins, device=y.device, dtype=torch.float32)
-            out['hist_centers'] = sd.lo + (k + 0.5) * ((sd.hi - sd.lo) / sd.bins)
-        if quantiles is not None:
-            if hist is None:
-                raise AssertionError('cFlow.sample: quantiles needs hist=(bins, lo, hi)')
-            levels = [float(q) for q in quantiles]
-            if not 1 <= len(levels) <= 8:
-                raise AssertionError(f'cFlow.sample: 1..8 quantile levels, got {len(levels)}')
-            sd.num_quantiles = len(levels)
-            for j, q in enumerate(levels):
-                sd.quantiles[j] = q
-            out['quantiles'] = torch.empty((len(levels), B, H, W, x_d), device=y.device, dtype=torch.float32)
+        B = int(y.shape[0])
+        sd, truth = _score_setup(out, (B, H, W, self.x_d), int(desc.num_samples), y.device, truth, hist, quantiles,
+                                 return_sq_err)
         check(_lib.load().cnf_flow_sample_score(
             self._plan, ptr(self.params), ptr(self._aux), ptr(y), C.byref(desc), C.byref(sd), ptr(truth),
             ptr(out.get('samples')), ptr(out.get('mean')), ptr(out.get('std')), ptr(out.get('y_dev')),
@@ -924,3 +933,142 @@ class cFlow:
         for t, v in zip(self.metrics, (loss, lz, ly, ld)):
             t.update_state(v)
         return {t.name: t.result() for t in self.metrics}
+
+
+# ---------------------------------------------------------------------------------------------
+# cascaded super-resolution
+# ---------------------------------------------------------------------------------------------
+
+class cFlowCascade:
+    """Multi-level super-resolution at inference: cFlow models trained independently per level
+    (conv_cINN.py:28-30, one for 'SR4,2', one for 'SR2,1'), chained. The up-scaled degraded image conditions
+    the first flow; each of its draws, up-scaled with `up`, conditions the second; and so on for up to 4
+    stages. Every stage has the same x_d and io_d = 2 x_d, and twice the height and width of the one before."""
+
+    MAX_STAGES = 4
+
+    def __init__(self, flows: Sequence[cFlow]):
+        self.flows = list(flows)
+        if not 1 <= len(self.flows) <= self.MAX_STAGES:
+            raise ValueError(f'cFlowCascade: 1..{self.MAX_STAGES} stages, got {len(self.flows)}')
+        for l, f in enumerate(self.flows, 1):
+            H, W, D = f.io_shape
+            if D != 2 * f.x_d:
+                raise ValueError(f'cFlowCascade: stage {l}: io_shape {f.io_shape} needs io_d == 2 * x_d (x_d {f.x_d})')
+            if l == 1:
+                continue
+            q = self.flows[l - 2]
+            if f.x_d != q.x_d:
+                raise ValueError(f'cFlowCascade: stage {l}: x_d {f.x_d} differs from stage {l - 1}\'s {q.x_d}')
+            if [H, W] != [2 * q.io_shape[0], 2 * q.io_shape[1]]:
+                raise ValueError(f'cFlowCascade: stage {l}: io_shape {f.io_shape} must be twice stage {l - 1}\'s '
+                                 f'{q.io_shape} in height and width')
+            if f.device != q.device:
+                raise ValueError(f'cFlowCascade: stage {l}: device {f.device} differs from stage {l - 1}\'s {q.device}')
+        self.device = self.flows[0].device
+        self.x_d = self.flows[0].x_d
+        self._ws = {}
+
+    def default_offsets(self, B, num_samples, offset=0):
+        """The stages' streams one after the other: offset_l = offset + sum_{k<l} B N_k H_k W_k x_d."""
+        offs, N = [], 1
+        for f, S in zip(self.flows, num_samples):
+            offs.append(int(offset))
+            N *= int(S)
+            offset += B * N * f.io_shape[0] * f.io_shape[1] * self.x_d
+        return offs
+
+    def sample(self, y, num_samples, temperature=1.0, seed=0, offset=0, chunk=None, logit_a=None, residual=False,
+               return_samples=True, return_stats=True, return_stage_stats=False, return_y_dev=False,
+               return_block_dev=False, truth=None, hist=None, quantiles=None, return_sq_err=None):
+        """The distribution of the final high-resolution images given the degraded input, in one native call
+        (cnf_flow_sample_cascade). y: [B,H_1,W_1,x_d] (or [H_1,W_1,x_d]), `up` of the low-resolution image, as
+        preprocess_dataset_SR puts it in the y channels; num_samples = (S_1, ..., S_L): every node of stage l - 1
+        gets S_l children, so a condition has N_l = S_1 ... S_l nodes at stage l and N_L leaves.
+
+        The one rule: a node's condition is `up` of what cFlow.sample would have returned for its parent (after
+        de_logitify(., logit_a) and + y with residual, at every stage). The call equals, bit for bit, the chain
+        f1.sample(y, S_1) -> up -> f2.sample(., S_2) -> ... with the stage offsets below, but keeps only one chunk
+        of images per stage on the device: the tree is walked depth-first, `chunk` images per inverse call
+        (default min(B N_L, 64)), and no result depends on chunk, bit for bit.
+        temperature and offset: a scalar or one value per stage. A scalar offset places the stages' Philox streams
+        one after the other (default_offsets): offset_l = offset + sum_{k<l} B N_k H_k W_k x_d.
+
+        Returns a dict with the requested ones of: 'samples' [B,N_L,H_L,W_L,x_d] (the leaves, in node order:
+        leaf g's parent is g // S_L); 'mean', 'std' [B,H_L,W_L,x_d] over a condition's leaves (the posterior mean
+        and std of the high-resolution image); with return_stage_stats 'stage_mean', 'stage_std': lists of L
+        tensors [B,H_l,W_l,x_d] over the N_l nodes of each stage; 'y_dev': a list of L tensors [B,N_l], cFlow.sample's
+        y_dev of every node against its own condition; 'block_dev': a list of L tensors [B,N_l], the sum over 2x2
+        pixel blocks and channels of |mean over the block of (value - condition)|, the reference's stated check
+        that a super-resolved draw's blocks average back to its condition (conv_cINN.py:44), 0 when they do.
+        truth [B,H_L,W_L,x_d], hist=(bins, lo, hi), quantiles=, return_sq_err: cFlow.sample's scores of the N_L
+        leaves of each condition ('rank', 'abs_err', 'sq_err' [B,N_L], 'hist', 'hist_centers', 'quantiles')."""
+        lib = _lib.load()
+        L = len(self.flows)
+        y = _as_input(y, 'y')
+        H1, W1, _ = self.flows[0].io_shape
+        x_d = self.x_d
+        if y.dim() == 3:
+            y = y.unsqueeze(0)
+        if tuple(y.shape[1:]) != (H1, W1, x_d):
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {H1}, {W1}, {x_d}]')
+        S = [int(s) for s in num_samples]
+        if len(S) != L:
+            raise ValueError(f'num_samples needs one entry per stage ({L}), got {len(S)}')
+        B = int(y.shape[0])
+        N = [max(int(np.prod(S[:l + 1])), 0) for l in range(L)]
+        T = [float(t) for t in temperature] if isinstance(temperature, (list, tuple)) else [float(temperature)] * L
+        offs = ([int(o) for o in offset] if isinstance(offset, (list, tuple))
+                else self.default_offsets(B, [max(s, 0) for s in S], int(offset)))
+        if len(T) != L or len(offs) != L:
+            raise ValueError(f'temperature and offset: a scalar or one value per stage ({L})')
+        if chunk is None:
+            chunk = max(1, min(B * N[-1], 64))
+        desc = _lib.cnf_cascade_desc()
+        desc.num_stages, desc.chunk, desc.seed = L, int(chunk), int(seed) & (2 ** 64 - 1)
+        desc.logit_a, desc.residual = float(logit_a or 0.0), int(bool(residual))
+        for l in range(L):
+            desc.num_samples[l], desc.temperature[l], desc.offset[l] = S[l], T[l], offs[l] & (2 ** 64 - 1)
+        plans = (C.c_void_p * L)(*[f._plan.value for f in self.flows])
+        key = (B, int(chunk))
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(lib.cnf_cascade_workspace_bytes(plans, B, C.byref(desc)))
+            if nbytes <= 0:   # an argument error, as the reference's asserts
+                raise AssertionError(f'cFlowCascade.sample: {lib.cnf_last_error().decode()}')
+            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+
+        def new(*shape):
+            return torch.empty(shape, device=y.device, dtype=torch.float32)
+
+        def stage_shape(l):
+            return (B,) + tuple(self.flows[l].io_shape[:2]) + (x_d,)
+        out = {}
+        HL, WL, _ = self.flows[-1].io_shape
+        if return_samples:
+            out['samples'] = new(B, N[-1], HL, WL, x_d)
+        mean, std = [None] * L, [None] * L
+        if return_stage_stats:
+            mean, std = [new(*stage_shape(l)) for l in range(L)], [new(*stage_shape(l)) for l in range(L)]
+            out['stage_mean'], out['stage_std'] = mean, std
+        elif return_stats:
+            mean[-1], std[-1] = new(*stage_shape(L - 1)), new(*stage_shape(L - 1))
+        if return_stats:
+            out['mean'], out['std'] = mean[-1], std[-1]
+        y_dev, block_dev = [None] * L, [None] * L
+        if return_y_dev:
+            out['y_dev'] = y_dev = [new(B, N[l]) for l in range(L)]
+        if return_block_dev:
+            out['block_dev'] = block_dev = [new(B, N[l]) for l in range(L)]
+        sd = None
+        if truth is not None or hist is not None or quantiles is not None or return_sq_err:
+            sd, truth = _score_setup(out, stage_shape(L - 1), N[-1], y.device, truth, hist, quantiles, return_sq_err)
+
+        def ptrs(ts):
+            return (C.c_void_p * L)(*[ptr(t) for t in ts])
+        check(lib.cnf_flow_sample_cascade(
+            plans, ptrs([f.params for f in self.flows]), ptrs([f._aux for f in self.flows]), ptr(y), C.byref(desc),
+            None if sd is None else C.byref(sd), ptr(truth), ptr(out.get('samples')), ptr(out.get('rank')),
+            ptr(out.get('abs_err')), ptr(out.get('sq_err')), ptr(out.get('hist')), ptr(out.get('quantiles')),
+            ptrs(mean), ptrs(std), ptrs(y_dev), ptrs(block_dev), ptr(ws), B, _stream()), 'cnf_flow_sample_cascade')
+        return out

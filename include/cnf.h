@@ -271,6 +271,65 @@ int cnf_flow_sample_score(cnf_plan* plan, const float* params, const float* aux,
                           float* log_prob, int* rank, float* abs_err, float* sq_err, int* hist,
                           float* quantiles, void* workspace, int B, void* stream);
 
+/* Cascaded super-resolution sampling: L stages, 1 <= L <= 4, of flows trained independently per level
+ * (conv_cINN.py:28-30, one model for 'SR4,2', one for 'SR2,1'), chained at inference. All stages have the
+ * same x_d = C and io_d = 2C (y has x's depth); stage l+1's io shape is (2 H_l, 2 W_l, 2C). y [B][H_1][W_1][C]
+ * conditions stage 1 (`up` of the low-resolution image, what preprocess_dataset_SR puts in the y channels).
+ * Stage l has N_l = S_1 * ... * S_l nodes per condition; node g of the flat [B][N_l] order has parent
+ * g / S_l at stage l - 1 and condition b = g / N_l. For a node:
+ *   latent     temperature[l] * element offset[l] + (g*H_l*W_l + p)*x_d + c of the seed's stream:
+ *              cnf_flow_sample's rule with S replaced by N_l
+ *   condition  stage 1: y[b]; deeper: y_l = cnf_up (the 2x2 repeat) of the parent's value
+ *   value      v_l = the value cnf_flow_sample returns for (latent, y_l): x_hat of the stage's inverse,
+ *              de_logitify if logit_a, + y_l (the node's own input condition, not y_hat) if residual
+ * The one rule: the next stage's condition is `up` of what cnf_flow_sample would have returned. The cascade
+ * therefore equals, bit for bit, the composition of cnf_flow_sample calls on B*N_{l-1} conditions with
+ * cnf_up between them, without materialising any [B][N_l][...] tensor but the leaves (if asked for).
+ * Outputs: samples [B][N_L][H_L][W_L][C], the leaves; per stage mean_l, std_l [B][H_l][W_l][C] over the
+ * N_l nodes of a condition in node order (cnf_flow_sample's (K, S1, S2) fold with S = N_l); y_dev_l
+ * [B][N_l] as cnf_flow_sample's, against the node's own condition; block_dev_l [B][N_l], the reference's
+ * stated sanity check (conv_cINN.py:44: the 2x2 pixel blocks of the residual sum to 0):
+ *   block_dev = (float) sum over 2x2 blocks and c of | 0.25 * sum over the block's 4 pixels, row-major, of
+ *               ((double)v_l - (double)y_l) |, one wave per node, fp64 lane sums over (block, c) in element
+ *               order, then the fixed-order wave sum; 0 for a draw whose `down` reproduces its condition;
+ * and on the leaves, with S = N_L, cnf_flow_sample_score's rank, abs_err, sq_err, hist, quantiles.
+ * Traversal: depth-first in node order with one chunk buffer per stage: stage-1 nodes run `chunk` at a
+ * time; the S_{l+1} children of each node of a finished chunk run through the next stage `chunk` at a
+ * time (a child chunk may straddle parents and conditions). Every stage visits its nodes in increasing g,
+ * the folds are cnf_flow_sample's serial folds, and no result depends on chunk, bit for bit. */
+typedef struct cnf_cascade_desc {
+    int   num_stages;       /* L in 1..4 */
+    int   num_samples[4];   /* S_l >= 1 children per parent node (stage 1: draws per condition) */
+    int   chunk;            /* images per inverse call of every stage, >= 1 */
+    float temperature[4];   /* per stage, finite and >= 0 */
+    uint64_t seed;
+    uint64_t offset[4];     /* per stage; to put the stages' streams one after the other:
+                               offset[l] = offset[l-1] + B*N_{l-1}*H_{l-1}*W_{l-1}*x_d */
+    float logit_a;          /* as cnf_sample_desc, applied at every stage */
+    int   residual;
+} cnf_cascade_desc;
+
+/* Workspace bytes: the sum over the stages of cnf_plan_sample_workspace_bytes(plans[l], B, chunk) (that
+ * plan's inverse workspace for `chunk` images, one chunk each of zy and xy_hat, the 3*B*H_l*W_l*x_d
+ * statistics state); independent of every S_l. 0 for a NULL or invalid argument (cnf_last_error). */
+size_t cnf_cascade_workspace_bytes(const cnf_plan* const* plans, int B, const cnf_cascade_desc* desc);
+
+/* plans, params, aux: arrays of L entries. mean, std, y_dev, block_dev: NULL or arrays of L per-stage
+ * pointers, each entry may be NULL. score / truth / rank .. quantiles: cnf_flow_sample_score's, on the
+ * leaves (truth [B][H_L][W_L][C]). At least one output must be requested. CNF_E_INVALID before any HIP
+ * call, the message naming the argument (and the stage where one is at fault), for: every case
+ * cnf_flow_sample / cnf_flow_sample_score reject, per stage where it applies; num_stages outside 1..4; a
+ * NULL plans / params / aux array or entry; io_d != 2 x_d; an x_d or io-shape mismatch between consecutive
+ * stages; N_L beyond 2^31 - 1; block_dev at a stage with odd H or W; no output. The launches are recorded on the plan of the stage they belong to (measurement
+ * hooks): k_latent / k_child_latent, the inverse's, k_sample_fold_node, k_sample_ydev_node,
+ * k_block_dev, k_sample_score_node, k_sample_sqerr_node, k_sample_quantiles. */
+int cnf_flow_sample_cascade(cnf_plan* const* plans, const float* const* params, const float* const* aux,
+                            const float* y, const cnf_cascade_desc* desc,
+                            const cnf_sample_score_desc* score, const float* truth, float* samples,
+                            int* rank, float* abs_err, float* sq_err, int* hist, float* quantiles,
+                            float* const* mean, float* const* std, float* const* y_dev,
+                            float* const* block_dev, void* workspace, int B, void* stream);
+
 /* The density of given images: the counterpart of cnf_flow_sample. x[B][H][W][x_d] lives in the space
  * of the returned samples (after de_logitify and the residual); every image is scored against its own
  * condition (paired) or against each of K conditions (pairwise), N = B or B*K pairs, pair i =
