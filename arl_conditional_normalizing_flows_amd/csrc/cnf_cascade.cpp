@@ -2,7 +2,8 @@
 // cnf_sample.hip): L flows chained, each stage's draws `up`-scaled into the next stage's conditions, the
 // tree of nodes walked depth-first with one chunk buffer per stage. Per chunk of a stage: its zy (k_latent at
 // stage 1, k_child_latent from the parent chunk's buffers below it), that plan's inverse schedule
-// (cnf_schedule.cpp), the folds of cnf_sampling.cpp with the image's own condition, then the chunk's children.
+// (cnf_schedule.cpp), cnf_sampling.cpp's record_chunk_outputs with the image's own condition, then the chunk's
+// children.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -20,9 +21,15 @@ const char* const WHO = "cnf_flow_sample_cascade";
 std::string stage(int l) { return "stage " + std::to_string(l + 1) + ": "; }
 
 // the argument errors that need the plans, B and the descriptor alone (empty: none)
-std::string cascade_desc_error(const cnf_plan* const* plans, int B, const cnf_cascade_desc* s) {
+// the descriptor itself and its stage count, which everything else reads (null: fine)
+const char* stages_error(const cnf_cascade_desc* s) {
     if (s == nullptr) return "null cascade descriptor";
     if (s->num_stages < 1 || s->num_stages > MAX_STAGES) return "num_stages must be in 1..4";
+    return nullptr;
+}
+
+std::string cascade_desc_error(const cnf_plan* const* plans, int B, const cnf_cascade_desc* s) {
+    if (const char* e = stages_error(s)) return e;
     if (plans == nullptr) return "null plans array";
     for (int l = 0; l < s->num_stages; l++)
         if (plans[l] == nullptr) return stage(l) + "null plan";
@@ -84,51 +91,12 @@ struct Cascade {
         const bool leaf = l == L - 1;
         const long long first = l == 0 ? 0 : pg0 * s.S, last = l == 0 ? (long long)B * s.N : (pg0 + pn) * s.S;
         const double px = (double)d.io_h * d.io_w;
-        const int per = d.io_h * d.io_w * d.x_d;   // elements per condition
-        const bool stats = s.mean != nullptr || s.std != nullptr;
-        float* const out = leaf ? samples : nullptr;
         float *zy = s.zy, *xy = s.xy;
-        SampleFoldArgs fa;
-        std::memset(&fa, 0, sizeof(fa));
-        fa.xy_hat = xy;
-        fa.zy = zy;
-        fa.samples = out;
-        fa.state = stats ? s.state : nullptr;
-        fa.mean = s.mean;
-        fa.std = s.std;
-        fa.B = B;
-        fa.logit = logit;
-        fa.residual = residual;
-        fa.lk = lk;
-        const bool scores = leaf && (sc.rank || sc.abs_err || sc.hist);
-        SampleScoreArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        SampleSqerrArgs qa;
-        std::memset(&qa, 0, sizeof(qa));
-        if (leaf && sc.any()) {
-            sa.xy_hat = xy;
-            sa.zy = zy;
-            sa.truth = sc.truth;
-            sa.rank = sc.rank;
-            sa.abs_err = sc.abs_err;
-            sa.hist = sc.hist;
-            sa.logit = logit;
-            sa.residual = residual;
-            sa.lk = lk;
-            if (sc.hist) {
-                sa.bins = sc.sd->bins;
-                sa.lo = sc.sd->lo;
-                sa.scale = (float)sc.sd->bins / (sc.sd->hi - sc.sd->lo);
-            }
-            qa.xy_hat = xy;
-            qa.zy = zy;
-            qa.truth = sc.truth;
-            qa.sq_err = sc.sq_err;
-            qa.logit = logit;
-            qa.residual = residual;
-            qa.lk = lk;
-        }
-        const BlockDevArgs ba{xy, zy, s.block_dev, d.io_w, logit, residual, lk};
+        const DrawView v{xy, zy, nullptr, logit, residual, lk};   // a node's condition: its own zy
+        float* const state = s.mean != nullptr || s.std != nullptr ? s.state : nullptr;
+        // the leaves alone are returned and scored
+        const ChunkOutputs out{leaf ? samples : nullptr, state, s.mean, s.std, s.y_dev, s.block_dev, /*log_prob=*/nullptr,
+                               leaf ? sc : ScoreArgs(), B};
         InverseOpts io;
         io.append = true;   // one recording per plan for the whole call
         for (long long g0 = first; g0 < last; g0 += chunk) {
@@ -144,35 +112,15 @@ struct Cascade {
                     E.record("k_latent", 0, 4.0 * n * px * (2 * d.io_d - d.x_d),
                              [=](void* q) { launch_latent(c, y1, zy, T, sd_, off, (hipStream_t)q); });
                 } else {
-                    const ChildLatentArgs ca{st[l - 1].xy, st[l - 1].zy, zy, pg0, s.S, d.io_w, s.T, seed, s.off, logit,
-                                             residual, lk};
+                    const DrawView parent{st[l - 1].xy, st[l - 1].zy, nullptr, logit, residual, lk};
+                    const ChildLatentArgs ca{parent, zy, pg0, s.S, d.io_w, s.T, seed, s.off};
                     // the parents' x_hat (and y with the residual) once, the chunk's zy written
                     E.record("k_child_latent", 0,
                              4.0 * n * px * d.io_d + 4.0 * ((double)n / s.S + 1) * (px / 4) * d.x_d * (residual ? 2 : 1),
                              [=](void* q) { launch_child_latent(c, ca, (hipStream_t)q); });
                 }
                 flow_inverse(p, s.params, s.aux, zy, xy, s.ws, n, stream, io);
-                if (out != nullptr || stats)
-                    E.record("k_sample_fold_node", 0, 4.0 * n * px * d.x_d * ((out ? 2 : 1) + (residual ? 1 : 0)),
-                             [=](void* q) { launch_sample_fold(c, fa, (hipStream_t)q); });
-                if (s.y_dev != nullptr) {
-                    float* y_dev = s.y_dev;
-                    E.record("k_sample_ydev_node", 0, 8.0 * n * px * (d.io_d - d.x_d),
-                             [=](void* q) { launch_sample_ydev_node(c, xy, zy, y_dev, (hipStream_t)q); });
-                }
-                if (s.block_dev != nullptr)
-                    E.record("k_block_dev", 0, 8.0 * n * px * d.x_d,
-                             [=](void* q) { launch_block_dev(c, ba, (hipStream_t)q); });
-                if (scores) {
-                    const double nb = (double)((g0 + n - 1) / s.N - g0 / s.N + 1);
-                    const double rmw = (sc.rank ? 8.0 : 0.0) + (sc.abs_err ? 8.0 : 0.0) + (sc.hist ? 8.0 * sa.bins : 0.0);
-                    E.record("k_sample_score_node", 0,
-                             4.0 * n * px * d.x_d * (residual ? 2 : 1) + nb * per * ((sc.truth ? 4.0 : 0.0) + rmw),
-                             [=](void* q) { launch_sample_score(c, sa, (hipStream_t)q); });
-                }
-                if (leaf && sc.sq_err != nullptr)
-                    E.record("k_sample_sqerr_node", 0, 4.0 * n * px * d.x_d * (residual ? 3 : 2),
-                             [=](void* q) { launch_sample_sqerr(c, qa, (hipStream_t)q); });
+                record_chunk_outputs(E, c, v, out);
             }
             if (!leaf) run(l + 1, g0, n);
         }
@@ -203,9 +151,10 @@ int cnf_flow_sample_cascade(cnf_plan* const* plans, const float* const* params, 
                             float* quantiles, float* const* mean, float* const* std, float* const* y_dev,
                             float* const* block_dev, void* workspace, int B, void* stream) {
     const std::string w = std::string(WHO) + ": ";
-    if (desc == nullptr) return fail(CNF_E_INVALID, w + "null cascade descriptor");
-    if (desc->num_stages < 1 || desc->num_stages > MAX_STAGES) return fail(CNF_E_INVALID, w + "num_stages must be in 1..4");
+    if (const char* e = stages_error(desc)) return fail(CNF_E_INVALID, w + e);
     const int L = desc->num_stages;
+    // the pointer checks come before the descriptor's other errors, stage by stage: cascade_desc_error's own
+    // null-plan tests cannot stand in for these without changing which message a caller with two errors sees
     if (!plans || !params || !aux) return fail(CNF_E_INVALID, w + "null plans, params or aux array");
     for (int l = 0; l < L; l++) {
         if (!plans[l]) return fail(CNF_E_INVALID, w + stage(l) + "null plan");
@@ -282,10 +231,8 @@ int cnf_flow_sample_cascade(cnf_plan* const* plans, const float* const* params, 
         Plan& p = *s.p;
         OptScope os_(&p.opts);
         const cnf_flow_desc& d = p.desc;
-        const SampleQuantileArgs ua = quantile_args(cs.sc, (long long)B * d.io_h * d.io_w * d.x_d);
         Exec E{p, s.params, s.aux, s.ws, p.layout(1), 1, cs.stream};
-        E.record("k_sample_quantiles", 0, 4.0 * (double)ua.n * (ua.bins + ua.nq),
-                 [=](void* q) { launch_sample_quantiles(ua, (hipStream_t)q); });
+        record_quantiles(E, cs.sc, (long long)B * d.io_h * d.io_w * d.x_d);
     }
     check_launch();
     return CNF_OK;

@@ -194,6 +194,15 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// A wave-per-image reduction (k_sample_logp, k_block_dev): lane sums in fp64 of term(e) over the image's
+// elements e = lane, lane + 64, ... < n in order, then the fixed-order wave sum
+template <class Term>
+__device__ __forceinline__ double wave_image_sum(int n, int lane, Term term) {
+    double s = 0.0;
+    for (int e = lane; e < n; e += 64) s += term(e);
+    return wave_sum(s);
+}
+
 // Sum of image img's log-det partial slots part[((l * B) + img) * np + j] over nl layers and np parts, by
 // one wave: lane k folds entries k, k + 64, ... (four loads in flight together), then the fixed-order wave
 // sum. The one summation order of every per-image log-det total (k_ld_reduce, k_sample_logp).

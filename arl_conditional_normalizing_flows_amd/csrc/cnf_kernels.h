@@ -568,65 +568,67 @@ struct SampleChunk {
 // of image g, pixel p, channel c is stream element offset + (g * HW + p) * x_d + c (instance_noise_value)
 void launch_latent(const SampleChunk& c, const float* y, float* zy, float temperature, unsigned long long seed,
                    unsigned long long offset, hipStream_t st);
+// Where a chunk's draws live and where a draw's condition comes from: the one view every kernel after a
+// chunk's inverse reads. The rule, stated here once: with y non-null the condition of image i of the chunk is
+// y[b], b = (g0 + i) / S (cnf_flow_sample); with y null it is the y channels of the image's own zy[i], which
+// the inverse leaves intact (cnf_flow_sample_cascade: at stage >= 2 a node's condition is `up` of its parent's
+// value, not y[b]). The kernels that read a condition are templates on that source (NODE: the image's own zy;
+// recorded with the suffix _node); same arithmetic, same bits. A draw's sample value is
+// sample_post_value(x_hat, logit, lk, residual, condition) (cnf_device.h), the one arithmetic expression.
+struct DrawView {
+    const float* xy_hat;  // the chunk's inverse output [n][HW][D]: x_hat on the channels < x_d
+    const float* zy;      // the chunk's latent [n][HW][D]: z on the channels < x_d, the condition on the rest
+    const float* y;       // the per-condition table [B][HW][D - x_d], or null: the image's own zy
+    int logit, residual;  // the post-transforms: de_logitify, + condition (needs D - x_d == x_d)
+    LogitK lk;
+    bool node() const { return y == nullptr; }
+};
 // k_sample_fold: one pass over the chunk's xy_hat. Per element (b, p, c < x_d) of the conditions the
-// chunk touches, over the chunk's draws of b in draw order: v = x_hat, de_logitify if logit, + y[b] if
-// residual; stored to samples [B][S][HW][x_d] (non-null); folded into state [3][B][HW][x_d] = (K, S1, S2)
+// chunk touches, over the chunk's draws of b in draw order: v = the draw's sample value; stored to samples
+// [B][S][HW][x_d] (non-null); folded into state [3][B][HW][x_d] = (K, S1, S2)
 // (sample_fold; loaded unless the chunk holds b's first draw), and with b's last draw mean / std
 // [B][HW][x_d] (each may be null) are written. state == null: no statistics.
 struct SampleFoldArgs {
-    const float* xy_hat;
-    const float* y;
+    DrawView v;
     float* samples;
     float* state;
     float* mean;
     float* std;
-    int B, logit, residual;
-    LogitK lk;
-    const float* zy;      // non-null (cascade): the condition of image i is the y channels of zy[i], not y[b]
+    int B;
 };
 void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream_t st);
-// k_sample_ydev: y_dev[g0 + i] = sum_{p, c >= x_d} |xy_hat[i, p, c] - y[(g0 + i) / S, p, c - x_d]|, one
+// k_sample_ydev: y_dev[g0 + i] = sum_{p, c >= x_d} |xy_hat[i, p, c] - condition[p, c - x_d]|, one
 // wave per image, fp64 lane sums in element order then a fixed-order wave sum
-void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st);
-// k_sample_ydev_node: the same against the image's own condition, the y channels of the chunk's zy (which the
-// inverse leaves intact)
-void launch_sample_ydev_node(const SampleChunk& c, const float* xy_hat, const float* zy, float* y_dev, hipStream_t st);
+void launch_sample_ydev(const SampleChunk& c, const DrawView& v, float* y_dev, hipStream_t st);
 // k_sample_logp: log_prob[g0 + i] = (float)(-0.5 q - 0.5 n log(2 pi) + L), n = HW * x_d, q the fp64 sum of
 // z^2 over image i's latent (channels < x_d of the chunk's zy), L the fp64 sum of image i's log-det slots
 // ld_part[nl][c.n][np] as the chunk's inverse wrote them (k_ld_reduce's order); one wave per image
 void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
                         hipStream_t st);
-// Scoring the draws against a truth (cnf_flow_sample_score). v below is k_sample_fold's sample value
-// (sample_post_value, cnf_device.h). The outputs are the state between chunks: a chunk that holds b's first
+// Scoring the draws against a truth (cnf_flow_sample_score). v below is k_sample_fold's sample value.
+// The outputs are the state between chunks: a chunk that holds b's first
 // draw initialises b's entries, every other chunk loads them, so nothing is read that this call did not write.
 // k_sample_score: k_sample_fold's ownership (a workgroup owns a tile of elements of one condition b over the
 // chunk's draws of b). rank[b,p,c] += #{v < truth} (null: none); abs_err[b,p,c]: the fp32 running sum of
 // |v - truth| in draw order, divided by S with b's last draw (null: none); hist[b,p,c,k] += the draws with
 // k == (int)floorf((v - lo) * scale), 0 <= k < bins (null: none; out of range and NaN dropped).
 struct SampleScoreArgs {
-    const float* xy_hat;
-    const float* y;
+    DrawView v;
     const float* truth;   // [B][HW][x_d]; needed by rank and abs_err
     int* rank;
     float* abs_err;
     int* hist;            // [B][HW][x_d][bins]
-    int logit, residual, bins;
+    int bins;
     float lo, scale;     // scale = (float)bins / (hi - lo)
-    LogitK lk;
-    const float* zy;      // as SampleFoldArgs::zy
 };
 constexpr int SCORE_MAX_BINS = 256, SCORE_MAX_QUANTILES = 8;
 void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStream_t st);
 // k_sample_sqerr: sq_err[g0 + i] = (float) sum_{p, c < x_d} ((double)v - (double)truth[(g0 + i) / S, p, c])^2,
 // one wave per image, fp64 lane sums in element order then the fixed-order wave sum
 struct SampleSqerrArgs {
-    const float* xy_hat;
-    const float* y;
+    DrawView v;
     const float* truth;
     float* sq_err;        // [B][S]
-    int logit, residual;
-    LogitK lk;
-    const float* zy;      // as SampleFoldArgs::zy
 };
 void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st);
 // k_sample_quantiles, once after the last chunk, one thread per element: quantiles[j][b][p][c] of level q[j] from
@@ -642,36 +644,29 @@ struct SampleQuantileArgs {
 void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st);
 
 // ---- cascaded sampling (cnf_sample.hip, cnf_flow_sample_cascade) --------------------------------
-// The kernels above with a non-null zy (k_sample_fold_node, k_sample_score_node, k_sample_sqerr_node) and
-// k_sample_ydev_node take each image's condition from the y channels of its own zy: at stage >= 2 of a
-// cascade a node's condition is `up` of its parent's value, not y[b]. Same arithmetic, same bits.
 // k_child_latent: one chunk c of a child stage's zy from the parent stage's chunk buffers. Child node g has
 // parent g / Sc, image g / Sc - pg0 of the parent chunk. Per child pixel (h, w): the x channels get
-// temperature * N(0,1) by k_latent's rule; y channel cy gets the parent's value at pixel (h / 2, w / 2):
-// sample_post_value(parent xy_hat[.., cy], logit, residual, parent zy[.., x_d + cy]) -- the post-transform,
+// temperature * N(0,1) by k_latent's rule; y channel cy gets the parent's sample value (its view, its own
+// condition) at pixel (h / 2, w / 2), channel cy -- the post-transform,
 // cnf_up and k_latent in one pass, the parent's image never written at full size. D == 2 x_d.
 struct ChildLatentArgs {
-    const float* pxy;     // the parent chunk's xy_hat [pn][HW / 4][D]
-    const float* pzy;     // the parent chunk's zy (its y channels: the parent's own condition)
+    DrawView parent;      // the parent chunk's buffers [pn][HW / 4][D]; y null
     float* zy;            // the child chunk's zy [n][HW][D]
     long long pg0;        // first node of the parent chunk
     int Sc, W;            // children per parent; the child's width
     float temperature;
     unsigned long long seed, offset;
-    int logit, residual;
-    LogitK lk;
 };
 void launch_child_latent(const SampleChunk& c, const ChildLatentArgs& a, hipStream_t st);
 // k_block_dev: block_dev[g0 + i] = (float) sum over the 2x2 pixel blocks and channels c < x_d of
 // |0.25 * sum over the block's 4 pixels in row-major order of ((double)v - (double)y)|, v the image's sample value,
-// y its condition (the y channels of zy[i]; D == 2 x_d, H and W even). One wave per image, fp64 lane sums over
+// y its condition (the y channels of zy[i], whatever the view's source: k_latent copied y[b] there; D == 2 x_d,
+// H and W even). One wave per image, fp64 lane sums over
 // (block, c) in element order, then the fixed-order wave sum.
 struct BlockDevArgs {
-    const float* xy_hat;
-    const float* zy;
+    DrawView v;
     float* block_dev;     // [B][S]
-    int W, logit, residual;
-    LogitK lk;
+    int W;
 };
 void launch_block_dev(const SampleChunk& c, const BlockDevArgs& a, hipStream_t st);
 

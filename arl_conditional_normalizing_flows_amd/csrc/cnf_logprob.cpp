@@ -6,8 +6,7 @@
 #include <cstring>
 #include <string>
 
-#include "cnf_api.h"
-#include "cnf_plan.h"
+#include "cnf_sampling.h"
 
 using namespace cnf;
 
@@ -23,17 +22,12 @@ LogpLayout logp_layout(const Plan& p, int chunk) {
     const cnf_flow_desc& d = p.desc;
     const size_t n_uv = (size_t)d.io_h * d.io_w * d.io_d;
     LogpLayout L;
-    size_t off = align_up(p.layout(chunk).total, 256);
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    L.xy = take((size_t)chunk * n_uv * 4);
-    L.zy = take((size_t)chunk * n_uv * 4);
-    L.ld = take((size_t)chunk * 4);
-    L.lj = take((size_t)chunk * logp_parts(d.io_h * d.io_w) * 8);
-    L.total = off;
+    WsCarver ws(p.layout(chunk).total);
+    L.xy = ws.take((size_t)chunk * n_uv * 4);
+    L.zy = ws.take((size_t)chunk * n_uv * 4);
+    L.ld = ws.take((size_t)chunk * 4);
+    L.lj = ws.take((size_t)chunk * logp_parts(d.io_h * d.io_w) * 8);
+    L.total = ws.off;
     return L;
 }
 
@@ -43,11 +37,7 @@ const char* logp_desc_error(const Plan& p, int B, const cnf_logp_desc* s) {
     if (B < 1) return "B must be >= 1";
     if (s->num_conditions < 0) return "num_conditions must be >= 1 (pairwise) or 0 (paired)";
     if (s->chunk < 1) return "chunk must be >= 1";
-    if (s->logit_a != 0.f && !(s->logit_a > 0.f && s->logit_a < 0.5f))
-        return "logit_a must be 0 (no logit map) or in (0, 0.5)";
-    if (s->residual != 0 && p.desc.io_d - p.desc.x_d != p.desc.x_d)
-        return "residual needs y of x's depth (io_d - x_d == x_d)";
-    return nullptr;
+    return post_transform_error(p, s->logit_a, s->residual, LogitWord::logit_map);
 }
 
 }  // namespace

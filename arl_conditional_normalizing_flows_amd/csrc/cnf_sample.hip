@@ -12,12 +12,13 @@
 //                       channels, k_latent's normals on the x channels (cnf_flow_sample_cascade)
 //   k_block_dev         per image sum over 2x2 pixel blocks of |block mean of (sample - condition)|
 // k_sample_fold, k_sample_ydev, k_sample_score and k_sample_sqerr are templates on where an image's condition
-// comes from: y[b] (cnf_flow_sample) or the y channels of its own zy (the cascade's nodes).
+// comes from (NODE; DrawView, cnf_kernels.h).
 // All HBM-bound element / reduction kernels; no global atomics (k_sample_score counts with integer LDS adds
 // inside the tile its workgroup owns), every floating-point sum in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "cnf_device.h"
 
@@ -59,67 +60,97 @@ __global__ __launch_bounds__(256) void k_latent(SampleChunk q, const float* __re
 // the chunk go through LDS in batches of FOLD_BATCH
 constexpr int FOLD_E = 32, FOLD_L = 8, FOLD_BATCH = 64;
 
-// A workgroup owns FOLD_E elements (p, c) of one condition b of those the chunk touches (b0 .. b0 + nb - 1;
-// bpc workgroups per condition). The post-transform of a value does not depend on the other draws, so all
-// 256 threads apply it, thread (e, l) to the draws l, l + FOLD_L, ... of a batch (their loads in flight
-// together: the draws are an image apart), store the sample and leave the value in LDS; the fold is a
-// serial chain per element, three operations a draw, which thread (e, 0) runs over the batch in draw order.
-// The draws s0 .. s1 - 1 of b in the chunk are the same for the whole workgroup: the barriers sit in
-// uniform control flow.
-// NODE (cnf_flow_sample_cascade, a.zy non-null): the residual's y is the draw's own condition, the y channel
-// of its image of the chunk's zy, loaded next to the value; everything else, the arithmetic included, is the same.
+// What a thread of k_sample_fold / k_sample_score owns. A workgroup owns FOLD_E elements (p, c) of one
+// condition b of those the chunk touches (b0 .. b0 + nb - 1; bpc workgroups per condition); thread (e, l)
+// takes the draws l, l + FOLD_L, ... of a batch (their loads in flight together: the draws are an image
+// apart). The draws s0 .. s1 - 1 of b in the chunk are the same for the whole workgroup, so barriers inside
+// the batch loop sit in uniform control flow.
+// NODE: the residual's y is the draw's own condition, the y channel of its image of the chunk's zy, loaded
+// next to the value; otherwise y[b]'s element, loaded once (D - x_d == x_d: y[b] has x's shape).
+template <bool NODE>
+struct FoldTile {
+    static constexpr int NJ = FOLD_BATCH / FOLD_L;
+    int per, e, l, pc0, pc, p, c, s0, s1;   // per: elements per condition
+    long long b, gb;                        // the condition, its first image
+    bool valid;
+    size_t plane, se, img;   // the elements of a [B][HW][x_d] tensor (B given), this thread's; of an image
+    const float *__restrict__ src, *__restrict__ ysrc;   // in image 0 of the chunk: the element, its condition
+    float yv, w[NJ], yw[NODE ? NJ : 1];                  // y[b]'s value; the batch as loaded
+
+    __device__ __forceinline__ FoldTile(const SampleChunk& q, const DrawView& v, long long b0, int bpc, int B = 0) {
+        per = q.HW * q.x_d;
+        b = b0 + blockIdx.x / bpc;
+        e = threadIdx.x % FOLD_E, l = threadIdx.x / FOLD_E;
+        pc0 = (blockIdx.x % bpc) * FOLD_E, pc = pc0 + e;
+        valid = pc < per;
+        p = pc / q.x_d, c = pc - p * q.x_d;
+        gb = b * q.S;
+        const long long g1 = q.g0 + q.n;
+        s0 = (int)((q.g0 > gb ? q.g0 : gb) - gb);
+        s1 = (int)((g1 < gb + q.S ? g1 : gb + q.S) - gb);
+        plane = (size_t)B * per;
+        se = (size_t)b * per + pc;
+        yv = !NODE && v.residual && valid ? v.y[se] : 0.f;
+    }
+    // before the batch loop (after the kernel's own loads and barriers, where the kernels have always done it)
+    __device__ __forceinline__ void sources(const SampleChunk& q, const DrawView& v) {
+        img = (size_t)q.HW * q.D;
+        src = v.xy_hat + (size_t)p * q.D + c;
+        ysrc = NODE ? v.zy + (size_t)p * q.D + q.x_d + c : nullptr;
+    }
+    // the batch that starts at draw sb: every load first
+    __device__ __forceinline__ void load(const SampleChunk& q, const DrawView& v, int sb) {
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int s = sb + l + j * FOLD_L;
+            w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
+            if constexpr (NODE) yw[j] = v.residual && valid && s < s1 ? ysrc[(size_t)(gb + s - q.g0) * img] : 0.f;
+        }
+    }
+    // the sample value of the batch's draw sb + l + j * FOLD_L
+    __device__ __forceinline__ float value(const DrawView& v, int j) const {
+        return sample_post_value(w[j], v.logit, v.lk, v.residual, NODE ? yw[j] : yv);
+    }
+};
+
+// The post-transform of a value does not depend on the other draws, so all 256 threads apply it, store the
+// sample and leave the value in LDS; the fold is a serial chain per element, three operations a draw, which
+// thread (e, 0) runs over the batch in draw order.
 template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldArgs a, long long b0, int bpc) {
     __shared__ float sh[FOLD_BATCH][FOLD_E];
-    const int per = q.HW * q.x_d;   // elements per condition
-    const long long b = b0 + blockIdx.x / bpc;
-    const int e = threadIdx.x % FOLD_E, l = threadIdx.x / FOLD_E;
-    const int pc = (blockIdx.x % bpc) * FOLD_E + e;
-    const bool valid = pc < per;
-    const int p = pc / q.x_d, c = pc - p * q.x_d;
-    const long long gb = b * q.S, g1 = q.g0 + q.n;
-    const int s0 = (int)((q.g0 > gb ? q.g0 : gb) - gb);
-    const int s1 = (int)((g1 < gb + q.S ? g1 : gb + q.S) - gb);
-    const size_t plane = (size_t)a.B * per;   // state: [3][B][HW][x_d]
-    const size_t se = (size_t)b * per + pc;
+    FoldTile<NODE> t(q, a.v, b0, bpc, a.B);
+    const size_t plane = t.plane;   // state: [3][B][HW][x_d]
+    const size_t se = t.se;
     const bool stats = a.state != nullptr;
-    const bool folds = stats && valid && l == 0;
-    const float yv = !NODE && a.residual && valid ? a.y[se] : 0.f;   // (D - x_d == x_d: y[b] has x's shape)
+    const bool folds = stats && t.valid && t.l == 0;
     float K = 0.f, S1 = 0.f, S2 = 0.f;
-    if (folds && s0 > 0) {
+    if (folds && t.s0 > 0) {
         K = a.state[se];
         S1 = a.state[plane + se];
         S2 = a.state[2 * plane + se];
     }
-    const size_t img = (size_t)q.HW * q.D;
-    const float* __restrict__ src = a.xy_hat + (size_t)p * q.D + c;   // the element in image 0 of the chunk
-    const float* __restrict__ ysrc = NODE ? a.zy + (size_t)p * q.D + q.x_d + c : nullptr;   // its condition
-    for (int sb = s0; sb < s1; sb += FOLD_BATCH) {
-        float w[FOLD_BATCH / FOLD_L], yw[NODE ? FOLD_BATCH / FOLD_L : 1];
+    t.sources(q, a.v);
+    for (int sb = t.s0; sb < t.s1; sb += FOLD_BATCH) {
+        t.load(q, a.v, sb);
 #pragma unroll
-        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
-            const int s = sb + l + j * FOLD_L;
-            w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
-            if constexpr (NODE) yw[j] = a.residual && valid && s < s1 ? ysrc[(size_t)(gb + s - q.g0) * img] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
-            const int s = sb + l + j * FOLD_L;
-            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, NODE ? yw[j] : yv);
-            if (valid && s < s1 && a.samples != nullptr) a.samples[(size_t)(gb + s) * per + pc] = v;
-            if (stats) sh[l + j * FOLD_L][e] = v;
+        for (int j = 0; j < t.NJ; j++) {
+            const int s = sb + t.l + j * FOLD_L;
+            const float v = t.value(a.v, j);
+            if (t.valid && s < t.s1 && a.samples != nullptr) a.samples[(size_t)(t.gb + s) * t.per + t.pc] = v;
+            if (stats) sh[t.l + j * FOLD_L][t.e] = v;
         }
         if (!stats) continue;
         __syncthreads();
         if (folds) {
-            const int nk = s1 - sb < FOLD_BATCH ? s1 - sb : FOLD_BATCH;
+            const int nk = t.s1 - sb < FOLD_BATCH ? t.s1 - sb : FOLD_BATCH;
 #pragma unroll 8
-            for (int k = 0; k < nk; k++) sample_fold(sh[k][e], sb + k == 0, K, S1, S2);
+            for (int k = 0; k < nk; k++) sample_fold(sh[k][t.e], sb + k == 0, K, S1, S2);
         }
         __syncthreads();
     }
     if (!folds) return;
-    if (s1 < q.S) {
+    if (t.s1 < q.S) {
         a.state[se] = K;
         a.state[plane + se] = S1;
         a.state[2 * plane + se] = S2;
@@ -131,19 +162,22 @@ __global__ __launch_bounds__(256) void k_sample_fold(SampleChunk q, SampleFoldAr
     }
 }
 
-// one wave per image of the chunk; lane sums in fp64 over its elements in order, then the wave sum
-// NODE: y is the chunk's zy, and image i's condition its y channels
+// The wave-per-image kernels: one wave per image of the chunk (whole waves past it leave); lane sums in fp64 over
+// the image's elements in order, then the wave sum: wave_image_sum (cnf_device.h) of a term per element in
+// k_sample_logp and k_block_dev; k_sample_ydev and k_sample_sqerr spell the same loop out, because through the
+// helper the compiler schedules their prologues differently. The wave's image:
+__device__ __forceinline__ int wave_image() { return blockIdx.x * 4 + (threadIdx.x >> 6); }
+
+// y_dev: |y_hat - condition| over the image's HW * (D - x_d) condition elements
 template <bool NODE>
-__global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, const float* __restrict__ xy_hat,
-                                                     const float* __restrict__ y, float* __restrict__ y_dev) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= q.n) return;   // (whole waves)
+__global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, DrawView v, float* __restrict__ y_dev) {
+    const int lane = threadIdx.x & 63, i = wave_image();
+    if (i >= q.n) return;
     const long long g = q.g0 + i;
     const long long b = g / q.S;
     const int yd = q.D - q.x_d, n = q.HW * yd;
-    const float* __restrict__ xi = xy_hat + (size_t)i * q.HW * q.D;
-    const float* __restrict__ yb = NODE ? y + (size_t)i * q.HW * q.D : y + (size_t)b * n;
+    const float* __restrict__ xi = v.xy_hat + (size_t)i * q.HW * q.D;
+    const float* __restrict__ yb = NODE ? v.zy + (size_t)i * q.HW * q.D : v.y + (size_t)b * n;
     double s = 0.0;
     for (int e = lane; e < n; e += 64) {
         const int p = e / yd, c = e - p * yd;
@@ -154,25 +188,21 @@ __global__ __launch_bounds__(256) void k_sample_ydev(SampleChunk q, const float*
     if (lane == 0) y_dev[g] = (float)s;
 }
 
-// one wave per image of the chunk: log_prob[g] = log N(z; 0, I) + sum over couplings of sum s, from the
-// chunk's latent (the x channels of zy as stored) and the log-det partial slots part[nl][n][np] the
-// chunk's inverse left in its workspace. q = sum z^2: fp64 lane sums over the image's HW * x_d latent
-// elements in element order, then the wave sum; L: the slots in k_ld_reduce's order (ld_slot_sum).
+// log_prob[g] = log N(z; 0, I) + sum over couplings of sum s, from the chunk's latent (the x channels of zy as
+// stored) and the log-det partial slots part[nl][n][np] the chunk's inverse left in its workspace. q = sum z^2
+// over the image's HW * x_d latent elements; L: the slots in k_ld_reduce's order (ld_slot_sum).
 __global__ __launch_bounds__(256) void k_sample_logp(SampleChunk q, const float* __restrict__ zy,
                                                      const double* __restrict__ part, int nl, int np,
                                                      float* __restrict__ log_prob) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= q.n) return;   // (whole waves)
+    const int lane = threadIdx.x & 63, i = wave_image();
+    if (i >= q.n) return;
     const int n = q.HW * q.x_d;
     const float* __restrict__ zi = zy + (size_t)i * q.HW * q.D;
-    double s = 0.0;
-    for (int e = lane; e < n; e += 64) {
+    const double s = wave_image_sum(n, lane, [=](int e) {
         const int p = e / q.x_d, c = e - p * q.x_d;
         const double z = (double)zi[(size_t)p * q.D + c];
-        s += z * z;
-    }
-    s = wave_sum(s);
+        return z * z;
+    });
     const double L = ld_slot_sum(part, q.n, i, nl, np, lane);
     if (lane == 0) log_prob[q.g0 + i] = (float)(-0.5 * s - 0.5 * (double)n * LOG_2PI_D + L);
 }
@@ -184,32 +214,25 @@ __global__ __launch_bounds__(256) void k_sample_logp(SampleChunk q, const float*
 constexpr int SCORE_EP = FOLD_E + 1;
 size_t score_lds_bytes(int bins) { return ((size_t)bins * SCORE_EP + FOLD_BATCH * FOLD_E + FOLD_L * FOLD_E) * 4; }
 
-// k_sample_fold's ownership and batches. Every thread (e, l) takes the draws l, l + FOLD_L, ... of a batch:
-// it counts those below the truth and adds their bins to the LDS tile (integer LDS adds: order-free);
+// k_sample_fold's ownership and batches (FoldTile). Every thread (e, l) counts its draws of a batch
+// below the truth and adds their bins to the LDS tile (integer LDS adds: order-free);
 // thread (e, 0) folds |v - truth| over the batch in draw order. The chunk's counts then go to the outputs,
 // which the workgroup owns: added to what the earlier chunks left there, or stored when the chunk holds
 // b's first draw. s0, s1 and the null tests are the same for the whole workgroup: the barriers are uniform.
-// NODE: as k_sample_fold's.
 template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScoreArgs a, long long b0, int bpc) {
     extern __shared__ __align__(16) int score_lds[];
     int* hs = score_lds;
     float* sh = reinterpret_cast<float*>(score_lds + a.bins * SCORE_EP);
     int* rk = score_lds + a.bins * SCORE_EP + FOLD_BATCH * FOLD_E;
-    const int per = q.HW * q.x_d;   // elements per condition
-    const long long b = b0 + blockIdx.x / bpc;
-    const int e = threadIdx.x % FOLD_E, l = threadIdx.x / FOLD_E;
-    const int pc0 = (blockIdx.x % bpc) * FOLD_E, pc = pc0 + e;
-    const bool valid = pc < per;
-    const int p = pc / q.x_d, c = pc - p * q.x_d;
-    const long long gb = b * q.S, g1 = q.g0 + q.n;
-    const int s0 = (int)((q.g0 > gb ? q.g0 : gb) - gb);
-    const int s1 = (int)((g1 < gb + q.S ? g1 : gb + q.S) - gb);
-    const bool first = s0 == 0;
-    const size_t se = (size_t)b * per + pc;
+    FoldTile<NODE> t(q, a.v, b0, bpc);
+    const int per = t.per, e = t.e, l = t.l, pc0 = t.pc0, s1 = t.s1;
+    const bool valid = t.valid;
+    const long long b = t.b;
+    const bool first = t.s0 == 0;
+    const size_t se = t.se;
     const bool owner = valid && l == 0;
     const bool errs = a.abs_err != nullptr, hist = a.hist != nullptr;
-    const float yv = !NODE && a.residual && valid ? a.y[se] : 0.f;
     const float tv = a.truth != nullptr && valid ? a.truth[se] : 0.f;
     float acc = errs && owner && !first ? a.abs_err[se] : 0.f;
     int below = 0;
@@ -217,21 +240,13 @@ __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScore
         for (int i = threadIdx.x; i < a.bins * SCORE_EP; i += 256) hs[i] = 0;
         __syncthreads();
     }
-    const size_t img = (size_t)q.HW * q.D;
-    const float* __restrict__ src = a.xy_hat + (size_t)p * q.D + c;   // the element in image 0 of the chunk
-    const float* __restrict__ ysrc = NODE ? a.zy + (size_t)p * q.D + q.x_d + c : nullptr;   // its condition
-    for (int sb = s0; sb < s1; sb += FOLD_BATCH) {
-        float w[FOLD_BATCH / FOLD_L], yw[NODE ? FOLD_BATCH / FOLD_L : 1];
+    t.sources(q, a.v);
+    for (int sb = t.s0; sb < s1; sb += FOLD_BATCH) {
+        t.load(q, a.v, sb);
 #pragma unroll
-        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
+        for (int j = 0; j < t.NJ; j++) {
             const int s = sb + l + j * FOLD_L;
-            w[j] = valid && s < s1 ? src[(size_t)(gb + s - q.g0) * img] : 0.f;   // (s >= s0: image gb + s - g0 >= 0)
-            if constexpr (NODE) yw[j] = a.residual && valid && s < s1 ? ysrc[(size_t)(gb + s - q.g0) * img] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < FOLD_BATCH / FOLD_L; j++) {
-            const int s = sb + l + j * FOLD_L;
-            const float v = sample_post_value(w[j], a.logit, a.lk, a.residual, NODE ? yw[j] : yv);
+            const float v = t.value(a.v, j);
             if (valid && s < s1) {
                 below += v < tv ? 1 : 0;
                 if (hist) {
@@ -275,24 +290,23 @@ __global__ __launch_bounds__(256) void k_sample_score(SampleChunk q, SampleScore
     }
 }
 
-// one wave per image of the chunk, as k_sample_ydev; NODE: the residual's y from image i's zy
+// sq_err: (sample value - truth)^2 over the image's HW * x_d elements
 template <bool NODE>
 __global__ __launch_bounds__(256) void k_sample_sqerr(SampleChunk q, SampleSqerrArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= q.n) return;   // (whole waves)
+    const int lane = threadIdx.x & 63, i = wave_image();
+    if (i >= q.n) return;
     const long long g = q.g0 + i;
     const long long b = g / q.S;
     const int n = q.HW * q.x_d;
-    const float* __restrict__ xi = a.xy_hat + (size_t)i * q.HW * q.D;
+    const float* __restrict__ xi = a.v.xy_hat + (size_t)i * q.HW * q.D;
     const float* __restrict__ tb = a.truth + (size_t)b * n;
     // (read with residual only: y[b] has x's shape)
-    const float* __restrict__ yb = NODE ? a.zy + (size_t)i * q.HW * q.D : a.y + (size_t)b * n;
+    const float* __restrict__ yb = NODE ? a.v.zy + (size_t)i * q.HW * q.D : a.v.y + (size_t)b * n;
     double s = 0.0;
     for (int e = lane; e < n; e += 64) {
         const int p = e / q.x_d, c = e - p * q.x_d;
-        const float yv = a.residual ? (NODE ? yb[(size_t)p * q.D + q.x_d + c] : yb[e]) : 0.f;
-        const float v = sample_post_value(xi[(size_t)p * q.D + c], a.logit, a.lk, a.residual, yv);
+        const float yv = a.v.residual ? (NODE ? yb[(size_t)p * q.D + q.x_d + c] : yb[e]) : 0.f;
+        const float v = sample_post_value(xi[(size_t)p * q.D + c], a.v.logit, a.v.lk, a.v.residual, yv);
         const double d = (double)v - (double)tb[e];
         s += d * d;
     }
@@ -335,9 +349,9 @@ __global__ __launch_bounds__(256) void k_sample_quantiles(SampleQuantileArgs a) 
 }
 
 // k_latent's threads and stores for one chunk of a child stage of a cascade. The x channels: k_latent's
-// normal. A y channel cy: the parent's sample value at pixel (h / 2, w / 2) -- sample_post_value of the parent
-// chunk's xy_hat with the parent's own condition (the y channels of the parent chunk's zy) -- i.e. cnf_up of the
-// value k_sample_fold would have stored for the parent, which is never written. D == 2 x_d.
+// normal. A y channel cy: the parent's sample value at pixel (h / 2, w / 2) -- the parent chunk's draw through
+// its view, with the parent's own condition -- i.e. cnf_up of the value k_sample_fold would have stored for the
+// parent, which is never written. D == 2 x_d.
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_child_latent(SampleChunk q, ChildLatentArgs a) {
     constexpr int V = VEC ? 4 : 1;
@@ -362,8 +376,8 @@ __global__ __launch_bounds__(256) void k_child_latent(SampleChunk q, ChildLatent
                 v[j] = a.temperature * instance_noise_value(0.f, false, 0.f, a.seed, z0 + c);
             } else {
                 const int cy = c - q.x_d;
-                const float yv = a.residual ? a.pzy[pe + q.x_d + cy] : 0.f;
-                v[j] = sample_post_value(a.pxy[pe + cy], a.logit, a.lk, a.residual, yv);
+                const float yv = a.parent.residual ? a.parent.zy[pe + q.x_d + cy] : 0.f;
+                v[j] = sample_post_value(a.parent.xy_hat[pe + cy], a.parent.logit, a.parent.lk, a.parent.residual, yv);
             }
         }
         if constexpr (VEC)
@@ -373,18 +387,15 @@ __global__ __launch_bounds__(256) void k_child_latent(SampleChunk q, ChildLatent
     }
 }
 
-// one wave per image of the chunk, as k_sample_ydev: lane sums in fp64 over the image's (2x2 block, channel)
-// elements in order, then the wave sum. An element: the four pixels of the block in row-major order, each
-// (double)v - (double)y (exact), added in that order, times 0.25 (exact), its absolute value.
+// block_dev over the image's (2x2 block, channel) elements. An element: the four pixels of the block in
+// row-major order, each (double)v - (double)y (exact), added in that order, times 0.25 (exact), its absolute value.
 __global__ __launch_bounds__(256) void k_block_dev(SampleChunk q, BlockDevArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= q.n) return;   // (whole waves)
+    const int lane = threadIdx.x & 63, i = wave_image();
+    if (i >= q.n) return;
     const int bw = a.W / 2, n = (q.HW / 4) * q.x_d;
-    const float* __restrict__ xi = a.xy_hat + (size_t)i * q.HW * q.D;
-    const float* __restrict__ zi = a.zy + (size_t)i * q.HW * q.D;
-    double s = 0.0;
-    for (int e = lane; e < n; e += 64) {
+    const float* __restrict__ xi = a.v.xy_hat + (size_t)i * q.HW * q.D;
+    const float* __restrict__ zi = a.v.zy + (size_t)i * q.HW * q.D;
+    const double s = wave_image_sum(n, lane, [=](int e) {
         const int blk = e / q.x_d, c = e - blk * q.x_d;
         const int bh = blk / bw, bx = blk - bh * bw;
         double d = 0.0;
@@ -392,18 +403,24 @@ __global__ __launch_bounds__(256) void k_block_dev(SampleChunk q, BlockDevArgs a
         for (int k = 0; k < 4; k++) {
             const size_t o = (size_t)((2 * bh + (k >> 1)) * a.W + 2 * bx + (k & 1)) * q.D + c;
             const float yv = zi[o + q.x_d];
-            const float v = sample_post_value(xi[o], a.logit, a.lk, a.residual, yv);
+            const float v = sample_post_value(xi[o], a.v.logit, a.v.lk, a.v.residual, yv);
             d += (double)v - (double)yv;
         }
-        s += fabs(0.25 * d);
-    }
-    s = wave_sum(s);
+        return fabs(0.25 * d);
+    });
     if (lane == 0) a.block_dev[q.g0 + i] = (float)s;
 }
 
 int grid_for(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
+
+// The one dispatch on a view's source: f(std::true_type) for the image's own zy (NODE), f(std::false_type) for
+// the table y[b]. The two instantiations of a kernel stay separate kernels.
+template <class F>
+void by_source(const DrawView& v, F f) {
+    v.node() ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace
@@ -425,18 +442,15 @@ void launch_sample_fold(const SampleChunk& c, const SampleFoldArgs& a, hipStream
     const long long b0 = c.g0 / c.S, b1 = (c.g0 + c.n - 1) / c.S;
     const int nb = (int)(b1 - b0 + 1);
     const int bpc = (c.HW * c.x_d + FOLD_E - 1) / FOLD_E;   // workgroups per condition
-    if (a.zy != nullptr)
-        CNF_LAUNCH(k_sample_fold<true>, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
-    else
-        CNF_LAUNCH(k_sample_fold<false>, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
+    by_source(a.v, [&](auto node) {
+        CNF_LAUNCH(k_sample_fold<decltype(node)::value>, dim3((unsigned)nb * bpc), dim3(256), 0, st, c, a, b0, bpc);
+    });
 }
 
-void launch_sample_ydev(const SampleChunk& c, const float* xy_hat, const float* y, float* y_dev, hipStream_t st) {
-    CNF_LAUNCH(k_sample_ydev<false>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, y, y_dev);
-}
-
-void launch_sample_ydev_node(const SampleChunk& c, const float* xy_hat, const float* zy, float* y_dev, hipStream_t st) {
-    CNF_LAUNCH(k_sample_ydev<true>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, xy_hat, zy, y_dev);
+void launch_sample_ydev(const SampleChunk& c, const DrawView& v, float* y_dev, hipStream_t st) {
+    by_source(v, [&](auto node) {
+        CNF_LAUNCH(k_sample_ydev<decltype(node)::value>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, v, y_dev);
+    });
 }
 
 void launch_sample_logp(const SampleChunk& c, const float* zy, const double* ld_part, int nl, int np, float* log_prob,
@@ -448,17 +462,16 @@ void launch_sample_score(const SampleChunk& c, const SampleScoreArgs& a, hipStre
     const long long b0 = c.g0 / c.S, b1 = (c.g0 + c.n - 1) / c.S;
     const int nb = (int)(b1 - b0 + 1);
     const int bpc = (c.HW * c.x_d + FOLD_E - 1) / FOLD_E;   // workgroups per condition
-    if (a.zy != nullptr)
-        CNF_LAUNCH(k_sample_score<true>, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
-    else
-        CNF_LAUNCH(k_sample_score<false>, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a, b0, bpc);
+    by_source(a.v, [&](auto node) {
+        CNF_LAUNCH(k_sample_score<decltype(node)::value>, dim3((unsigned)nb * bpc), dim3(256), score_lds_bytes(a.bins), st, c, a,
+                   b0, bpc);
+    });
 }
 
 void launch_sample_sqerr(const SampleChunk& c, const SampleSqerrArgs& a, hipStream_t st) {
-    if (a.zy != nullptr)
-        CNF_LAUNCH(k_sample_sqerr<true>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
-    else
-        CNF_LAUNCH(k_sample_sqerr<false>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
+    by_source(a.v, [&](auto node) {
+        CNF_LAUNCH(k_sample_sqerr<decltype(node)::value>, dim3((c.n + 3) / 4), dim3(256), 0, st, c, a);
+    });
 }
 
 void launch_sample_quantiles(const SampleQuantileArgs& a, hipStream_t st) {

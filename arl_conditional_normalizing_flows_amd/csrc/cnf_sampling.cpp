@@ -2,7 +2,6 @@
 // per chunk, the inverse schedule (cnf_schedule.cpp) and the folds of the draws into the outputs.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <string>
 
 #include "cnf_sampling.h"
@@ -15,17 +14,21 @@ SampleLayout sample_layout(const Plan& p, int B, int chunk) {
     const cnf_flow_desc& d = p.desc;
     const size_t n_uv = (size_t)d.io_h * d.io_w * d.io_d;
     SampleLayout L;
-    size_t off = align_up(p.layout(chunk).total, 256);
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    L.zy = take((size_t)chunk * n_uv * 4);
-    L.xy = take((size_t)chunk * n_uv * 4);
-    L.state = take((size_t)3 * B * d.io_h * d.io_w * d.x_d * 4);
-    L.total = off;
+    WsCarver ws(p.layout(chunk).total);
+    L.zy = ws.take((size_t)chunk * n_uv * 4);
+    L.xy = ws.take((size_t)chunk * n_uv * 4);
+    L.state = ws.take((size_t)3 * B * d.io_h * d.io_w * d.x_d * 4);
+    L.total = ws.off;
     return L;
+}
+
+const char* post_transform_error(const Plan& p, float logit_a, int residual, LogitWord zero_means) {
+    if (logit_a != 0.f && !(logit_a > 0.f && logit_a < 0.5f))
+        return zero_means == LogitWord::delogitify ? "logit_a must be 0 (no de_logitify) or in (0, 0.5)"
+                                                   : "logit_a must be 0 (no logit map) or in (0, 0.5)";
+    if (residual != 0 && p.desc.io_d - p.desc.x_d != p.desc.x_d)
+        return "residual needs y of x's depth (io_d - x_d == x_d)";
+    return nullptr;
 }
 
 // the argument errors of cnf_flow_sample that need no pointer but the descriptor (null: fine)
@@ -35,11 +38,7 @@ const char* sample_desc_error(const Plan& p, int B, const cnf_sample_desc* s) {
     if (s->num_samples < 1) return "num_samples must be >= 1";
     if (s->chunk < 1) return "chunk must be >= 1";
     if (!(s->temperature >= 0.f) || std::isinf(s->temperature)) return "temperature must be finite and >= 0";
-    if (s->logit_a != 0.f && !(s->logit_a > 0.f && s->logit_a < 0.5f))
-        return "logit_a must be 0 (no de_logitify) or in (0, 0.5)";
-    if (s->residual != 0 && p.desc.io_d - p.desc.x_d != p.desc.x_d)
-        return "residual needs y of x's depth (io_d - x_d == x_d)";
-    return nullptr;
+    return post_transform_error(p, s->logit_a, s->residual, LogitWord::delogitify);
 }
 
 // the argument errors of the score part (no output given: none)
@@ -64,19 +63,59 @@ const char* score_error(const ScoreArgs& sc) {
     return nullptr;
 }
 
-// k_sample_quantiles' arguments for n elements, from the score descriptor
-SampleQuantileArgs quantile_args(const ScoreArgs& sc, long long n) {
-    SampleQuantileArgs ua;
-    std::memset(&ua, 0, sizeof(ua));
-    ua.hist = sc.hist;
-    ua.quantiles = sc.quantiles;
-    ua.n = n;
-    ua.bins = sc.sd->bins;
-    ua.nq = sc.sd->num_quantiles;
-    ua.lo = sc.sd->lo;
-    ua.hi = sc.sd->hi;
+void record_chunk_outputs(Exec& E, const SampleChunk& c, const DrawView& v, const ChunkOutputs& o) {
+    const ScoreArgs& sc = o.sc;
+    const int n = c.n, per = c.HW * c.x_d;   // elements per condition
+    const bool node = v.node();
+    const auto name = [&](const char* k) { return std::string(k) + (node ? "_node" : ""); };
+    const double xs = 4.0 * n * (double)c.HW * c.x_d;   // the chunk's x_hat once
+    const int cond = node && v.residual ? 1 : 0;        // ... and, in node form, its condition with every draw
+    if (o.samples != nullptr || o.state != nullptr) {
+        const SampleFoldArgs fa{v, o.samples, o.state, o.mean, o.std, o.B};
+        E.record(name("k_sample_fold"), 0, xs * ((o.samples ? 2 : 1) + cond),
+                 [=](void* st) { launch_sample_fold(c, fa, (hipStream_t)st); });
+    }
+    if (o.y_dev != nullptr) {
+        float* y_dev = o.y_dev;
+        E.record(name("k_sample_ydev"), 0, 8.0 * n * (double)c.HW * (c.D - c.x_d),
+                 [=](void* st) { launch_sample_ydev(c, v, y_dev, (hipStream_t)st); });
+    }
+    if (o.block_dev != nullptr) {
+        const BlockDevArgs ba{v, o.block_dev, E.p.desc.io_w};
+        E.record("k_block_dev", 0, 2 * xs, [=](void* st) { launch_block_dev(c, ba, (hipStream_t)st); });
+    }
+    if (o.log_prob != nullptr) {
+        // the slots the chunk's inverse just wrote
+        const double* ld = E.at<double>(E.L.ld);
+        const int nl = (int)E.p.couplings.size(), np = E.L.ld_parts;
+        float* log_prob = o.log_prob;
+        E.record("k_sample_logp", 0, xs + 8.0 * n * nl * np,
+                 [=](void* st) { launch_sample_logp(c, v.zy, ld, nl, np, log_prob, (hipStream_t)st); });
+    }
+    if (sc.rank || sc.abs_err || sc.hist) {
+        SampleScoreArgs sa{v, sc.truth, sc.rank, sc.abs_err, sc.hist, 0, 0.f, 0.f};
+        if (sc.hist) {
+            sa.bins = sc.sd->bins;
+            sa.lo = sc.sd->lo;
+            sa.scale = (float)sc.sd->bins / (sc.sd->hi - sc.sd->lo);
+        }
+        // per touched condition the truth and the read-modify-write of the outputs
+        const double nb = (double)((c.g0 + n - 1) / c.S - c.g0 / c.S + 1);
+        const double rmw = (sc.rank ? 8.0 : 0.0) + (sc.abs_err ? 8.0 : 0.0) + (sc.hist ? 8.0 * sa.bins : 0.0);
+        E.record(name("k_sample_score"), 0, xs * (1 + cond) + nb * per * ((sc.truth ? 4.0 : 0.0) + rmw),
+                 [=](void* st) { launch_sample_score(c, sa, (hipStream_t)st); });
+    }
+    if (sc.sq_err != nullptr) {
+        const SampleSqerrArgs qa{v, sc.truth, sc.sq_err};
+        E.record(name("k_sample_sqerr"), 0, xs * (2 + cond), [=](void* st) { launch_sample_sqerr(c, qa, (hipStream_t)st); });
+    }
+}
+
+void record_quantiles(Exec& E, const ScoreArgs& sc, long long n) {
+    SampleQuantileArgs ua{sc.hist, sc.quantiles, n, sc.sd->bins, sc.sd->num_quantiles, sc.sd->lo, sc.sd->hi, {}};
     for (int j = 0; j < ua.nq; j++) ua.q[j] = sc.sd->quantiles[j];
-    return ua;
+    E.record("k_sample_quantiles", 0, 4.0 * (double)ua.n * (ua.bins + ua.nq),   // (the second walk hits the cache)
+             [=](void* st) { launch_sample_quantiles(ua, (hipStream_t)st); });
 }
 
 }  // namespace cnf
@@ -108,38 +147,10 @@ int flow_sample(const char* who, cnf_plan* plan, const float* params, const floa
     char* ws = (char*)workspace;
     float* zy = reinterpret_cast<float*>(ws + SL.zy);
     float* xy = reinterpret_cast<float*>(ws + SL.xy);
-    const bool stats = mean != nullptr || std != nullptr;
-    SampleFoldArgs fa;
-    std::memset(&fa, 0, sizeof(fa));
-    fa.xy_hat = xy;
-    fa.y = y;
-    fa.samples = samples;
-    fa.state = stats ? reinterpret_cast<float*>(ws + SL.state) : nullptr;
-    fa.mean = mean;
-    fa.std = std;
-    fa.B = B;
-    fa.logit = desc->logit_a != 0.f ? 1 : 0;
-    fa.residual = desc->residual != 0 ? 1 : 0;
-    if (fa.logit) fa.lk = logit_consts(desc->logit_a);
-    const int per = d.io_h * d.io_w * d.x_d;   // elements per condition
-    const bool scores = sc.rank || sc.abs_err || sc.hist;
-    SampleScoreArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.xy_hat = xy;
-    sa.y = y;
-    sa.truth = sc.truth;
-    sa.rank = sc.rank;
-    sa.abs_err = sc.abs_err;
-    sa.hist = sc.hist;
-    sa.logit = fa.logit;
-    sa.residual = fa.residual;
-    sa.lk = fa.lk;
-    if (sc.hist) {
-        sa.bins = sc.sd->bins;
-        sa.lo = sc.sd->lo;
-        sa.scale = (float)sc.sd->bins / (sc.sd->hi - sc.sd->lo);
-    }
-    const SampleSqerrArgs qa{xy, y, sc.truth, sc.sq_err, fa.logit, fa.residual, fa.lk};
+    DrawView v{xy, zy, y, desc->logit_a != 0.f ? 1 : 0, desc->residual != 0 ? 1 : 0, LogitK{}};
+    if (v.logit) v.lk = logit_consts(desc->logit_a);
+    float* const state = mean != nullptr || std != nullptr ? reinterpret_cast<float*>(ws + SL.state) : nullptr;
+    const ChunkOutputs out{samples, state, mean, std, y_dev, /*block_dev=*/nullptr, log_prob, sc, B};
     const float T = desc->temperature;
     const unsigned long long seed = desc->seed, off = desc->offset;
     const long long total = (long long)B * desc->num_samples;
@@ -154,35 +165,11 @@ int flow_sample(const char* who, cnf_plan* plan, const float* params, const floa
         E.record("k_latent", 0, 4.0 * n * px * (2 * d.io_d - d.x_d),
                  [=](void* st) { launch_latent(c, y, zy, T, seed, off, (hipStream_t)st); });
         flow_inverse(p, params, aux, zy, xy, ws, n, (hipStream_t)stream, io);
-        if (samples != nullptr || stats)
-            E.record("k_sample_fold", 0, 4.0 * n * px * d.x_d * (samples ? 2 : 1),
-                     [=](void* st) { launch_sample_fold(c, fa, (hipStream_t)st); });
-        if (y_dev != nullptr)
-            E.record("k_sample_ydev", 0, 8.0 * n * px * (d.io_d - d.x_d),
-                     [=](void* st) { launch_sample_ydev(c, xy, y, y_dev, (hipStream_t)st); });
-        if (log_prob != nullptr) {
-            // the slots the chunk's inverse just wrote
-            const double* ld = E.at<double>(E.L.ld);
-            const int nl = (int)p.couplings.size(), np = E.L.ld_parts;
-            E.record("k_sample_logp", 0, 4.0 * n * px * d.x_d + 8.0 * n * nl * np,
-                     [=](void* st) { launch_sample_logp(c, zy, ld, nl, np, log_prob, (hipStream_t)st); });
-        }
-        if (scores) {
-            // xy_hat once; per touched condition the truth and the read-modify-write of the outputs
-            const double nb = (double)((g0 + n - 1) / desc->num_samples - g0 / desc->num_samples + 1);
-            const double rmw = (sc.rank ? 8.0 : 0.0) + (sc.abs_err ? 8.0 : 0.0) + (sc.hist ? 8.0 * sa.bins : 0.0);
-            E.record("k_sample_score", 0, 4.0 * n * px * d.x_d + nb * per * ((sc.truth ? 4.0 : 0.0) + rmw),
-                     [=](void* st) { launch_sample_score(c, sa, (hipStream_t)st); });
-        }
-        if (sc.sq_err != nullptr)
-            E.record("k_sample_sqerr", 0, 8.0 * n * px * d.x_d,
-                     [=](void* st) { launch_sample_sqerr(c, qa, (hipStream_t)st); });
+        record_chunk_outputs(E, c, v, out);
     }
     if (sc.quantiles != nullptr) {
-        const SampleQuantileArgs ua = quantile_args(sc, (long long)B * per);
         Exec E{p, params, aux, ws, p.layout(1), 1, (hipStream_t)stream};
-        E.record("k_sample_quantiles", 0, 4.0 * (double)ua.n * (ua.bins + ua.nq),   // (the second walk hits the cache)
-                 [=](void* st) { launch_sample_quantiles(ua, (hipStream_t)st); });
+        record_quantiles(E, sc, (long long)B * d.io_h * d.io_w * d.x_d);
     }
     check_launch();
     return CNF_OK;

@@ -43,6 +43,17 @@ def _as_input(t, what='input'):
     return t.contiguous()
 
 
+def _call_workspace(cache, key, device, who, nbytes):
+    """cache[key], or a new workspace of nbytes() bytes; <= 0: an argument error, as the reference's asserts"""
+    ws = cache.get(key)
+    if ws is None:
+        n = int(nbytes())
+        if n <= 0:
+            raise AssertionError(f'{who}: {_lib.load().cnf_last_error().decode()}')
+        ws = cache[key] = torch.empty(n, device=device, dtype=torch.uint8)
+    return ws
+
+
 def _score_setup(out, shape, S, device, truth, hist, quantiles, return_sq_err):
     """The score arguments of sample(): checks truth [B,H,W,x_d] = shape, allocates the requested score outputs
     into `out` for S draws per condition, and returns (cnf_sample_score_desc, truth)."""
@@ -649,12 +660,8 @@ class cFlow:
                                     int(offset) & (2 ** 64 - 1), float(logit_a or 0.0), int(bool(residual)))
         lib = _lib.load()
         key = ('sample', B, S, int(chunk))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(lib.cnf_plan_sample_workspace_bytes(self._plan, B, C.byref(desc)))
-            if nbytes <= 0:   # an argument error, as the reference's asserts
-                raise AssertionError(f'cFlow.sample: {lib.cnf_last_error().decode()}')
-            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        ws = _call_workspace(self._ws, key, self.device, 'cFlow.sample',
+                             lambda: lib.cnf_plan_sample_workspace_bytes(self._plan, B, C.byref(desc)))
 
         def new(*shape):
             return torch.empty(shape, device=y.device, dtype=torch.float32)
@@ -753,12 +760,8 @@ class cFlow:
         desc = _lib.cnf_logp_desc(K, int(chunk), float(logit_a or 0.0), int(bool(residual)))
         lib = _lib.load()
         key = ('log_prob', int(chunk))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(lib.cnf_plan_logp_workspace_bytes(self._plan, B, C.byref(desc)))
-            if nbytes <= 0:   # an argument error, as the reference's asserts
-                raise AssertionError(f'cFlow.log_prob: {lib.cnf_last_error().decode()}')
-            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        ws = _call_workspace(self._ws, key, self.device, 'cFlow.log_prob',
+                             lambda: lib.cnf_plan_logp_workspace_bytes(self._plan, B, C.byref(desc)))
 
         def new(*s):
             return torch.empty(s, device=x.device, dtype=torch.float32)
@@ -1031,12 +1034,8 @@ class cFlowCascade:
             desc.num_samples[l], desc.temperature[l], desc.offset[l] = S[l], T[l], offs[l] & (2 ** 64 - 1)
         plans = (C.c_void_p * L)(*[f._plan.value for f in self.flows])
         key = (B, int(chunk))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(lib.cnf_cascade_workspace_bytes(plans, B, C.byref(desc)))
-            if nbytes <= 0:   # an argument error, as the reference's asserts
-                raise AssertionError(f'cFlowCascade.sample: {lib.cnf_last_error().decode()}')
-            ws = self._ws[key] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        ws = _call_workspace(self._ws, key, self.device, 'cFlowCascade.sample',
+                             lambda: lib.cnf_cascade_workspace_bytes(plans, B, C.byref(desc)))
 
         def new(*shape):
             return torch.empty(shape, device=y.device, dtype=torch.float32)
