@@ -169,6 +169,8 @@ _DEBUG_SIGS = [
     ('cnf_debug_pw_shapes', C.c_int, [_P, C.c_int, _I, C.c_int]),
     ('cnf_debug_pw_words', C.c_int, []),
     ('cnf_debug_pw_ipw', C.c_int, [C.c_int] * 4),
+    # what cnf_flow_log_prob launches for a chunk of n pairs (gather kernel, tiles, grid, finish trips)
+    ('cnf_debug_logp_choice', C.c_int, [_P, C.c_int, C.c_int, _I, C.c_int]),
 ]
 
 _lib = None

@@ -242,6 +242,22 @@ int cnf_debug_pw_ipw(int tiles_per_img, int nprob, int res, int B) {
 // passes of k_grad_rows' image loop at batch B
 int cnf_debug_grad_rows_trips(int B) { return B < 1 ? -1 : grad_rows_trips(B); }
 
+// ---- the density of given images (tests/test_log_prob_sweep.py) ------------------------------------------------
+// What cnf_flow_log_prob launches for a chunk of n pairs on the plan's io shape, from the host functions the
+// launch code itself calls (logp_gather_choice, logp_parts, logp_per_xcd, logp_finish_trips); nothing is launched.
+// aligned: x, y and the workspace's xy are 16-byte aligned. Words: [gather kernel (LogpGatherKernel: 0
+// k_logp_gather_any, 1 <1,1>, 2 <3,1>, 3 <3,3>), parts (tiles and log_jac slots per image), per_xcd, the gather's
+// grid, k_logp_finish's trips over an image, threads of its last trip that hold a float4]
+int cnf_debug_logp_choice(const cnf_plan* plan, int n, int aligned, int* words, int cap) {
+    if (!plan || !words || cap < 6 || n < 1) return -1;
+    const cnf_flow_desc& d = plan->p->desc;
+    const int HW = d.io_h * d.io_w, parts = logp_parts(HW), per_xcd = logp_per_xcd(n, parts);
+    const int out[6] = {logp_gather_choice(d.x_d, d.io_d - d.x_d, HW, aligned != 0), parts, per_xcd, per_xcd * 8,
+                        logp_finish_trips(HW, d.io_d), logp_finish_last_trip(HW, d.io_d)};
+    std::memcpy(words, out, sizeof(out));
+    return 6;
+}
+
 // diagnostic builds: the phase stamps the kernels of the last stamped launch left
 int cnf_debug_read_stamps(long long* out, int n) { return read_stamps(out, n); }
 int cnf_debug_read_bwd_stamps(long long* out, int n) { return read_bwd_stamps(out, n); }

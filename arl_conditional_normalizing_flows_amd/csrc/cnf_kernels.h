@@ -686,6 +686,26 @@ struct LogpChunk {
 // HW pixels has logp_parts(HW) tiles and as many log_jac partial slots
 constexpr int LOGP_QUADS = 256;
 inline int logp_parts(int HW) { return (HW + 4 * LOGP_QUADS - 1) / (4 * LOGP_QUADS); }
+// the gather's grid for a chunk of n pairs: n * parts work items dealt over the 8 XCDs, per_xcd each (rounded up)
+inline int logp_per_xcd(int n, int parts) { return (n * parts + 7) / 8; }
+// Which gather runs (launch_logp_gather launches what this returns, cnf_debug_logp_choice reports it): the
+// float4 template of the presets' (x_d, D - x_d) = (1, 1), (3, 1), (3, 3) when HW % 4 == 0 and x, y and xy are
+// 16-byte aligned, k_logp_gather_any for every other depth or alignment
+enum LogpGatherKernel { LOGP_GATHER_ANY = 0, LOGP_GATHER_1_1 = 1, LOGP_GATHER_3_1 = 2, LOGP_GATHER_3_3 = 3 };
+inline LogpGatherKernel logp_gather_choice(int x_d, int yd, int HW, bool aligned) {
+    if (HW % 4 != 0 || !aligned) return LOGP_GATHER_ANY;
+    if (x_d == 1 && yd == 1) return LOGP_GATHER_1_1;
+    if (x_d == 3 && yd == 1) return LOGP_GATHER_3_1;
+    if (x_d == 3 && yd == 3) return LOGP_GATHER_3_3;
+    return LOGP_GATHER_ANY;
+}
+// k_logp_finish's element loop: a workgroup takes LOGP_FINISH_STEP floats of the image's HW * D per trip (one
+// float4 per thread); the threads of the last trip that still hold a float4 (256: the last trip is full)
+constexpr int LOGP_FINISH_STEP = 4 * 256;
+inline int logp_finish_trips(int HW, int D) { return (HW * D + LOGP_FINISH_STEP - 1) / LOGP_FINISH_STEP; }
+inline int logp_finish_last_trip(int HW, int D) {
+    return (HW * D - (logp_finish_trips(HW, D) - 1) * LOGP_FINISH_STEP + 3) / 4;
+}
 // k_logp_gather: xy[i] = concat(v, y[cond]) for the chunk's pairs, v = logit_value(x[img] - y[cond]) (the
 // subtraction with residual, the map with logit: sample_post_value's inverse), and the pair's log_jac
 // partials lj[i][part] = sum over the tile's x elements of -log(e (1 - e)), e = a + c1 x' in fp32 as the map

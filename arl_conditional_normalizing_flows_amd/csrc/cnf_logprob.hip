@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_logp_finish(LogpChunk q, LogpFinishArgs
     const float* __restrict__ zi = a.zy + (size_t)i * n;
     const float* __restrict__ yc = a.y + (size_t)cond * q.HW * yd;
     double zz = 0.0, dev = 0.0;
-    for (int e0 = 4 * (int)threadIdx.x; e0 < n; e0 += 4 * 256) {
+    for (int e0 = 4 * (int)threadIdx.x; e0 < n; e0 += LOGP_FINISH_STEP) {
         const f4 t = *reinterpret_cast<const f4*>(zi + e0);
         const float z[4] = {t.x, t.y, t.z, t.w};
         int p = e0 / q.D, c = e0 - p * q.D;
@@ -212,15 +212,16 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 
 void launch_logp_gather(const LogpChunk& c, const LogpGatherArgs& a, hipStream_t st) {
     const int parts = logp_parts(c.HW);
-    const int per_xcd = (c.n * parts + 7) / 8;
+    const int per_xcd = logp_per_xcd(c.n, parts);
     const dim3 grid((unsigned)per_xcd * 8);
-    const int yd = c.D - c.x_d;
-    const bool vec = c.HW % 4 == 0 && aligned16(a.x) && aligned16(a.y) && aligned16(a.xy);
-    // the presets' (x_d, D - x_d): (1, 1), (3, 1), (3, 3)
-    void (*k)(LogpChunk, LogpGatherArgs, int, int) = k_logp_gather_any;
-    if (vec && c.x_d == 1 && yd == 1) k = k_logp_gather<1, 1>;
-    if (vec && c.x_d == 3 && yd == 1) k = k_logp_gather<3, 1>;
-    if (vec && c.x_d == 3 && yd == 3) k = k_logp_gather<3, 3>;
+    void (*k)(LogpChunk, LogpGatherArgs, int, int) = nullptr;
+    switch (logp_gather_choice(c.x_d, c.D - c.x_d, c.HW, aligned16(a.x) && aligned16(a.y) && aligned16(a.xy))) {
+        case LOGP_GATHER_ANY: k = k_logp_gather_any; break;
+        case LOGP_GATHER_1_1: k = k_logp_gather<1, 1>; break;
+        case LOGP_GATHER_3_1: k = k_logp_gather<3, 1>; break;
+        case LOGP_GATHER_3_3: k = k_logp_gather<3, 3>; break;
+    }
+    if (k == nullptr) throw std::logic_error("k_logp_gather: no kernel for the choice");
     CNF_LAUNCH(k, grid, dim3(256), 0, st, c, a, parts, per_xcd);
 }
 
