@@ -61,6 +61,16 @@ class cnf_logp_desc(C.Structure):
     _fields_ = [('num_conditions', C.c_int), ('chunk', C.c_int), ('logit_a', C.c_float), ('residual', C.c_int)]
 
 
+class cnf_score_desc(C.Structure):
+    _fields_ = [('chunk', C.c_int), ('logit_a', C.c_float), ('residual', C.c_int)]
+
+
+class cnf_ascend_desc(C.Structure):
+    _fields_ = [('chunk', C.c_int), ('steps', C.c_int), ('lr', C.c_float), ('beta_1', C.c_float),
+                ('beta_2', C.c_float), ('epsilon', C.c_float), ('logit_a', C.c_float), ('residual', C.c_int),
+                ('first_step', C.c_int)]
+
+
 class cnf_toy_sample_desc(C.Structure):
     _fields_ = [('num_samples', C.c_int), ('temperature', C.c_float), ('seed', C.c_uint64), ('offset', C.c_uint64),
                 ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
@@ -106,6 +116,10 @@ _SIGS = [
     ('cnf_plan_logp_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_logp_desc)]),
     ('cnf_flow_log_prob', C.c_int, [_P, _F, _F, _F, _F, C.POINTER(cnf_logp_desc), _F, _F, _F, _F, _F, _F, _F, _F, _P,
                                     C.c_int, _P]),
+    ('cnf_plan_score_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_score_desc)]),
+    ('cnf_flow_score', C.c_int, [_P, _F, _F, _F, _F, C.POINTER(cnf_score_desc), _F, _F, _F, _P, C.c_int, _P]),
+    ('cnf_plan_ascend_workspace_bytes', C.c_size_t, [_P, C.c_int, C.POINTER(cnf_ascend_desc)]),
+    ('cnf_flow_ascend', C.c_int, [_P, _F, _F, _F, _F, C.POINTER(cnf_ascend_desc), _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_forward', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _P, C.c_int, _P]),
     ('cnf_coupling_inverse_logdet', C.c_int, [_P, C.c_int, _F, _F, _F, _F, _F, _P, C.c_int, _P]),

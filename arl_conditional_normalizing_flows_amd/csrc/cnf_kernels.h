@@ -741,6 +741,63 @@ void launch_logp_finish(const LogpChunk& c, const LogpFinishArgs& a, hipStream_t
 void launch_logp_posterior(const float* log_prob, const float* log_prior, float* posterior, float* log_evidence,
                            int B, int K, hipStream_t st);
 
+// ---- input gradients of the log-density (cnf_score.hip, cnf_flow_score / cnf_flow_ascend) -----------
+// The kernels around the data-gradient-only backward, on one chunk of paired images (LogpChunk with K == 0).
+// The reduction rule is the one stated above; none of them has an atomic or a counter.
+// k_score_seed: one workgroup per image and one pass over zy[i] (k_logp_finish's ownership of the elements):
+// dzy[i] = the seed of d(llz + logdet)/dzy, -z on the x channels and 0 on the others (null: not written), and
+// llz[i] = -0.5 sum z^2 - 0.5 HW x_d log(2 pi) in fp64. trace (may be null): trace[g0 + i] = (float)(llz[i] +
+// ld[i]), -inf for an image whose lj slots (null: none) sum to -inf: the flow-input-space log-density.
+struct ScoreSeedArgs {
+    const float* zy;     // [n][HW][D]
+    float* dzy;          // [n][HW][D] or null
+    double* llz;         // [n]
+    const float* ld;     // [n] the forward's per-image log-det (read only with trace)
+    const double* lj;    // [n][logp_parts(HW)] or null
+    float* trace;        // [B] or null
+};
+void launch_score_seed(const LogpChunk& c, const ScoreSeedArgs& a, hipStream_t st);
+// k_score_finish: the gradient g = d(llz + logdet)/dxy of the chunk ([n][HW][D], the backward's) through the
+// gather's map, per element of image g0 + i: with v = x - y (residual) or x, e = a + c1 v and u = logit_value(v),
+// t = g_x du/dv + d log_jac/dv = g_x c1 / (span e (1 - e)) - c1 (1 - 2 e) / (e (1 - e)) (without logit: t = g_x);
+// grad_x = t, grad_y = g_y (- t on channel c with residual). log_prob[g0 + i] = (float)(llz + ld + J) with
+// k_logp_finish's J. An image with J == -inf: log_prob -inf, its gradients NaN. Any output may be null. One
+// float4 of g per thread, grid (trips, n).
+struct ScoreFinishArgs {
+    const float* g;      // [n][HW][D] or null (no gradient asked for)
+    const float* x;      // [B][HW][x_d]
+    const float* y;      // [B][HW][D - x_d]
+    const double* llz;   // [n]
+    const float* ld;     // [n]
+    const double* lj;    // [n][parts]
+    double lj_const;
+    float *grad_x, *grad_y, *log_prob;
+    int logit, residual;
+    LogitK lk;
+};
+void launch_score_finish(const LogpChunk& c, const ScoreFinishArgs& a, hipStream_t st);
+// k_ascend_step: Keras Adam (k_adam's arithmetic) on the x channels of the chunk's xy with the gradient -g, so the
+// step climbs: gi = -g; m += (gi - m)(1 - b1); v += (gi^2 - v)(1 - b2); xy -= alpha m / (sqrt(v) + eps), in
+// place. m, v: [n][HW][x_d] (the chunk's part of the state). The y channels are not read or written.
+struct AscendStepArgs {
+    float* xy;           // [n][HW][D]
+    const float* g;      // [n][HW][D]
+    float *m, *v;
+    float alpha, b1, b2, eps;
+};
+void launch_ascend_step(const LogpChunk& c, const AscendStepArgs& a, hipStream_t st);
+// k_ascend_out: x_out[g0 + i] = sample_post_value(xy[i] x channels, condition y[g0 + i]) (de_logitify, + y), or
+// x0[g0 + i] for an image whose lj slots sum to -inf
+struct AscendOutArgs {
+    const float* xy;     // [n][HW][D]
+    const float* x0;     // [B][HW][x_d]
+    const float* y;      // [B][HW][D - x_d]
+    const double* lj;    // [n][parts]
+    float* x_out;        // [B][HW][x_d]
+    int logit, residual;
+    LogitK lk;
+};
+void launch_ascend_out(const LogpChunk& c, const AscendOutArgs& a, hipStream_t st);
 
 // ---- training (cnf_train.hip) -------------------------------------------------------------------
 // Generic fp32 convolution for the training path over the dense backward image (taps x k x n):

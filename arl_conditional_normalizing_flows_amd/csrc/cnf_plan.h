@@ -374,6 +374,16 @@ typedef void (*LayerDoneFn)(void* user, int coupling_index);
 void flow_backward(Plan& p, const float* params, const float* xy, const float* zy, void* workspace, int B,
                    float inv_batch, float* dparams, hipStream_t st, const float* count = nullptr,
                    LayerDoneFn done = nullptr, void* user = nullptr);
+// The data-gradient-only backward (cnf_score.cpp): from the seed dzy = dL/dzy [B][H][W][D] and dL/d(per-image
+// log-det) = +1, the gradient with respect to the flow's input xy, [B][H][W][D] in xy's layout; the returned
+// pointer lies in `workspace` (a duv buffer of the train layout of B) and holds until the next training call on
+// it. flow_backward's walk without every launch whose only outputs are parameter gradients (the weight
+// gradients and their scatters, the split LDS backward's second launch and its side stream, k_lnb_gsum,
+// k_dsum, k_grad_rows); no dparams, no layer_done. bw / zeros: the dense backward image [n_bw] and >= 64 floats
+// of zeros, filled by pack_backward_image once per native call (they outlive the per-chunk train layouts).
+const float* flow_backward_data(Plan& p, const float* params, const float* bw, const float* zeros, const float* dzy,
+                                void* workspace, int B, hipStream_t st);
+void pack_backward_image(Plan& p, const float* params, float* bw, float* zeros, hipStream_t st);
 // one coupling layer's backward: du, dparams (zeroed first) for dL/dv = dv and dL/d logdet_b = g_ld
 void coupling_layer_backward(Plan& p, int ci, const float* params, const float* u, const float* dv, float* du,
                              float g_ld, void* workspace, int B, float* dparams, hipStream_t st);

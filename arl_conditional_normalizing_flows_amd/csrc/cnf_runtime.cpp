@@ -175,7 +175,7 @@ using namespace cnf;
 extern "C" {
 
 const char* cnf_last_error(void) { return g_err.c_str(); }
-const char* cnf_version(void) { return "cnf-mi355x 0.1 (gfx950)"; }
+const char* cnf_version(void) { return "cnf-mi355x 0.2 (gfx950)"; }
 
 int cnf_plan_create(const cnf_flow_desc* desc, cnf_plan** out) {
     if (!out) return fail(CNF_E_INVALID, "null out");

@@ -281,8 +281,14 @@ struct TExec : Exec {
     bool saved = false;             // the training forward saved the streamed layers' activations (flow backward)
     int net = 0;                    // which per-net scratch set this executor's launches use
     hipStream_t wst = nullptr;      // weight-gradient stream (null: on st)
-    const float* bw() const { return at<const float>(T.bw); }
-    const float* zeros() const { return at<const float>(T.zeros); }
+    // data-gradient-only backward (flow_backward_data): no launch whose only outputs are parameter gradients,
+    // dparams null; bw_ / zeros_: the dense backward image and the zeros block the caller packed once per
+    // native call (null: the layout's own, filled by begin_backward)
+    bool data_only = false;
+    const float* bw_ = nullptr;
+    const float* zeros_ = nullptr;
+    const float* bw() const { return bw_ != nullptr ? bw_ : at<const float>(T.bw); }
+    const float* zeros() const { return zeros_ != nullptr ? zeros_ : at<const float>(T.zeros); }
     double* lnsum() const { return at<double>(T.lnsum[net]); }
 };
 
@@ -470,6 +476,7 @@ void wgrad_launch(const TExec& E, WGradArgs a, const PackedConv& pc, hipStream_t
 // waits for the chain's launches so far (its X and dY are ready) and returns the event of its completion
 // (null on the chain's own stream, where order alone protects dY)
 hipEvent_t conv_wgrad(TExec& E, Geom g, Src x, const LnIn& ln, Src dy, const PackedConv& pc, int dil) {
+    if (E.data_only) return nullptr;   // (no reader of dY on another stream either)
     const WGradArgs a = wgrad_args(E, g, x, ln, dy, pc, dil);
     if (E.wst == nullptr) {
         wgrad_launch(E, a, pc, E.st);
@@ -485,8 +492,10 @@ hipEvent_t conv_wgrad(TExec& E, Geom g, Src x, const LnIn& ln, Src dy, const Pac
 
 void ln_bwd(TExec& E, const float* x, const float* dxo, const LnIn& ln, long long n, float* dx, int accumulate,
             int64_t g_off, int64_t b_off, int presum = 0, unsigned long long cmask = 0, int cmod = 0) {
+    // (data-only: k_lnb_apply's gamma / beta partials stay in lnpart, no k_lnb_gsum)
+    const bool pg = ln.stats != nullptr && !E.data_only;
     launch_ln_backward(x, dxo, ln.gamma, ln.stats, E.lnsum(), n, E.B, 1, dx, accumulate,
-                       ln.stats ? E.dparams + g_off : nullptr, ln.stats ? E.dparams + b_off : nullptr,
+                       pg ? E.dparams + g_off : nullptr, pg ? E.dparams + b_off : nullptr,
                        E.at<float>(E.T.lnpart[E.net]), E.st, presum, LNR_MAXPARTS, cmask, cmod);
 }
 
@@ -545,7 +554,7 @@ void coupling_law_backward(TExec& E, const Coupling& c, const float* u, const fl
     a.dc2 = c.dc2;
     const int np = std::max(1, E.L.ld_parts);
     launch_coupling_backward(a, E.B, np, E.st);
-    launch_dsum(a.dw_part, (long long)E.B * np, E.dparams + c.net[0].tanh_w, E.st);
+    if (!E.data_only) launch_dsum(a.dw_part, (long long)E.B * np, E.dparams + c.net[0].tanh_w, E.st);
 }
 
 // du += the two nets' u1 gradients, net A's first (fixed order: bitwise reproducible)
@@ -594,16 +603,19 @@ hipEvent_t coupling_backward_lds(TExec& E, const Coupling& c, const float* u, co
     const NetParams& n1 = c.net[1];
     if (!split) {
         a.mode = 0;
-        launch_lds_bwd(a, B, E.st);
-        launch_grad_rows(a.part, B, a.row, n0.lo, n1.lo, (int)(n0.hi - n0.lo), (int)(n1.hi - n1.lo), E.dparams, E.st);
+        launch_lds_bwd(a, B, E.st);   // (data-only: as it is, its gradient rows stay in the workspace)
+        if (!E.data_only)
+            launch_grad_rows(a.part, B, a.row, n0.lo, n1.lo, (int)(n0.hi - n0.lo), (int)(n1.hi - n1.lo), E.dparams,
+                             E.st);
         scatter_du1c(E, c, du, E.st);
         return nullptr;
     }
-    ensure_side(E.p);
+    if (!E.data_only) ensure_side(E.p);
     a.gsave = E.at<float>(E.T.gsave[par]);
     a.mode = 1;
     launch_lds_bwd(a, B, E.st);
     scatter_du1c(E, c, du, E.st);
+    if (E.data_only) return nullptr;   // the chain alone: no weight-gradient launch, no side stream
     hipStream_t ws = E.p.wside[1];
     stream_wait(E.st, ws, tevent(E.p));   // the chain's stored gradients and LN rows
     a.mode = 2;
@@ -685,7 +697,7 @@ struct StreamedBwd {
         X[1].net = 1;
         X[1].st = E.p.side;
         for (int n = 0; n < 2; n++) {
-            X[n].wst = wstreams ? E.p.wside[n] : nullptr;
+            X[n].wst = wstreams && !E.data_only ? E.p.wside[n] : nullptr;
             const TrainLayout& T = E.T;
             S[n] = Scratch{{E.at<float>(T.dy[n])}, {E.at<float>(T.dt1[n])}, {E.at<float>(T.dt2[n])},
                            E.at<float>(T.dln[n]), E.at<float>(T.dbuf[n]), E.at<float>(T.dc[n]),
@@ -921,6 +933,57 @@ void flow_backward(Plan& p, const float* params, const float* xy, const float* z
     flush(last);
     flush(last ^ 1);
     hchk(hipGetLastError(), "training kernel launch");
+}
+
+const float* flow_backward_data(Plan& p, const float* params, const float* bw, const float* zeros, const float* dzy,
+                                void* workspace, int B, hipStream_t st) {
+    const TrainLayout TL = p.train_layout(B);
+    TExec E{{p, params, nullptr, (char*)workspace, p.layout(B), B, st}, nullptr, TL};
+    p.tev_next = 0;   // (as begin_backward: the previous call's waits are all enqueued)
+    E.data_only = true;
+    E.bw_ = bw;
+    E.zeros_ = zeros;
+    E.inv_batch_ = -1.f;   // dL/d(per-image log-det) = +1
+    E.saved = true;
+    const WsLayout& L = E.L;
+    const int* T = p.dev_table;
+    const int nuv = (int)L.n_uv;
+    float* buf[2] = {E.at<float>(E.T.duv[0]), E.at<float>(E.T.duv[1])};
+    int which = 0;
+    launch_map_gather(dzy, buf[which], T + p.dev_final_orig, p.last_n, nuv, p.last_n, B, st);
+    float* cur = buf[which];
+    which ^= 1;
+    int bi = (int)p.boundaries.size() - 1;
+    const bool split = opts().lds_bwd == 2;
+    int lds_k = 0;
+    for (int li = (int)p.layers.size() - 1; li >= 0; li--) {
+        const Layer& ly = p.layers[li];
+        if (ly.kind == CNF_LAYER_COUPLING) {
+            const Coupling& c = p.couplings[ly.ci];
+            float* nxt = buf[which];
+            const float* u = E.at<float>(E.T.save_u[c.index]);
+            if (c.lds_bwd)   // (split: the buffer sets alternate as in flow_backward; nothing runs behind the chain)
+                coupling_backward_lds(E, c, u, cur, nxt, split ? lds_k++ & 1 : -1);
+            else
+                StreamedBwd(E, c).run(u, cur, nxt);
+            cur = nxt;
+            which ^= 1;
+        } else if (ly.kind == CNF_LAYER_FACTOR) {
+            const Boundary& b = p.boundaries[bi--];
+            float* prev = buf[which];
+            launch_map_scatter(cur, prev, nullptr, T + b.dev_keep_src, b.n_next, b.n_next, b.n_cur, B, st);
+            launch_map_scatter(dzy, prev, T + b.dev_fac_orig, T + b.dev_fac_src, b.n_fac, nuv, b.n_cur, B, st);
+            cur = prev;
+            which ^= 1;
+        }
+    }
+    hchk(hipGetLastError(), "training kernel launch");
+    return cur;
+}
+
+void pack_backward_image(Plan& p, const float* params, float* bw, float* zeros, hipStream_t st) {
+    if (p.n_bw > 0) launch_pack(params, p.dev_bw_map, bw, (long long)p.n_bw, st);
+    hchk(hipMemsetAsync(zeros, 0, 64 * 4, st), "hipMemsetAsync");
 }
 
 void coupling_layer_backward(Plan& p, int ci, const float* params, const float* u, const float* dv, float* du,

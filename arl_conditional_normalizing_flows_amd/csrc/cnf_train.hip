@@ -1928,7 +1928,7 @@ void launch_ln_backward(const float* x, const float* dxo, const float* gamma, co
     float* bpart = scratch + (size_t)LNB_SLICES * n;
     hipLaunchKernelGGL(k_lnb_apply, dim3((unsigned)((n + 1023) / 1024), S), dim3(256), 0, st, x, dxo, gamma, stats,
                        sums, rsl, rstride, n, B, act, dx, accumulate, gpart, bpart, cmask, cmod);
-    if (stats)
+    if (stats && dgamma != nullptr)   // (null: the data-gradient-only backward leaves the partials in scratch)
         hipLaunchKernelGGL(k_lnb_gsum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gpart, bpart, S, n, dgamma,
                            dbeta);
 }

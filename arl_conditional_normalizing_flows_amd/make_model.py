@@ -779,6 +779,107 @@ class cFlow:
         out['bits_per_dim'] = out['log_prob'] * (-1.0 / (H * W * x_d * math.log(2.0)))
         return out
 
+    # -- input gradients of the log-density -------------------------------------------------------
+    def _paired_xy(self, x, y, who):
+        """x [B,H,W,x_d] and y [B,H,W,D-x_d] of a paired call ([H,W,.]: one image), checked as log_prob's"""
+        x, y = _as_input(x, 'x'), _as_input(y, 'y')
+        H, W, D = self.io_shape
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if y.dim() == 3:
+            y = y.unsqueeze(0)
+        if tuple(x.shape[1:]) != (H, W, self.x_d):
+            raise ValueError(f'x has shape {tuple(x.shape)}, expected [None, {H}, {W}, {self.x_d}]')
+        if tuple(y.shape[1:]) != (H, W, D - self.x_d):
+            raise ValueError(f'y has shape {tuple(y.shape)}, expected [None, {H}, {W}, {D - self.x_d}]')
+        if int(y.shape[0]) != int(x.shape[0]):
+            raise ValueError(f'{who} needs one condition per image: x holds {int(x.shape[0])}, y {int(y.shape[0])}')
+        return x, y
+
+    def score(self, x, y, logit_a=None, residual=False, chunk=None, return_grad_y=False):
+        """The gradient of the log-density with respect to the image and to the condition, in one native call
+        (cnf_flow_score): the exact derivative of log_prob(x, y, logit_a, residual)['log_prob'] (paired: image
+        b under condition b) as a function of x and of y.
+
+        x: [B,H,W,x_d], y: [B,H,W,D-x_d] on the device (or [H,W,.] for one image), as log_prob takes them. The
+        images run `chunk` at a time (default min(B, 64)) through the training forward and a backward that
+        computes data gradients only: no weight gradient is launched and no parameter gradient leaves it.
+
+        Returns a dict: 'grad_x' [B,H,W,x_d] = d log_prob[b] / d x[b]; 'log_prob' [B]; with return_grad_y
+        'grad_y' [B,H,W,D-x_d] = d log_prob[b] / d y[b] (through the condition channels of the flow's input and,
+        with residual, through x - y): the sensitivity of this reconstruction's density to its condition.
+        'log_prob' is independent of chunk, bit for bit. The gradients are equal across chunk only up to fp32
+        rounding: a streamed layer's data-gradient convolution (launch_tconv, k_tconv_band) picks its tile height
+        by the launch's workgroup count, which counts the chunk's images, and the tiles of an image are the fp64
+        partials its fused LayerNorm-backward reduction sums. (The LayerNorm backward's own batch slices touch
+        the gamma / beta partials only.)
+        An image with an element outside the logit map's domain has log_prob -inf and NaN gradients; the other
+        images are untouched."""
+        x, y = self._paired_xy(x, y, 'cFlow.score')
+        H, W, D = self.io_shape
+        B = int(x.shape[0])
+        if chunk is None:
+            chunk = max(1, min(B, 64))
+        desc = _lib.cnf_score_desc(int(chunk), float(logit_a or 0.0), int(bool(residual)))
+        lib = _lib.load()
+        ws = _call_workspace(self._ws, ('score', int(chunk)), self.device, 'cFlow.score',
+                             lambda: lib.cnf_plan_score_workspace_bytes(self._plan, B, C.byref(desc)))
+        out = {'grad_x': torch.empty_like(x), 'log_prob': torch.empty(B, device=x.device, dtype=torch.float32)}
+        if return_grad_y:
+            out['grad_y'] = torch.empty_like(y)
+        check(lib.cnf_flow_score(self._plan, ptr(self.params), ptr(self._aux), ptr(x), ptr(y), C.byref(desc),
+                                 ptr(out['grad_x']), ptr(out.get('grad_y')), ptr(out['log_prob']), ptr(ws), B,
+                                 _stream()), 'cnf_flow_score')
+        return out
+
+    def ascend(self, x, y, steps, lr=1e-2, beta_1=0.9, beta_2=0.999, epsilon=1e-7, logit_a=None, residual=False,
+               chunk=None, state=None, return_state=False):
+        """`steps` steps of Adam gradient ascent on the model's log-density from the images x, the conditions y
+        held fixed, in one native call without a host synchronisation between the steps (cnf_flow_ascend): a
+        most-probable reconstruction to put next to sample()'s mean, or the local refinement of a draw.
+
+        It climbs sample(return_log_prob=True)'s 'log_prob', llz + logdet, as a function of the flow's input:
+        x is taken into that space as log_prob does (- y when residual, the logit map when logit_a is given),
+        the ascent moves the x channels there, and the result comes back through sample()'s post-transforms.
+        The mode of a density depends on the parametrisation: with logit_a the iterate approaches a mode of the
+        density over the flow's (unconstrained) input space, in which the model was trained, and that is not the
+        mode of the density over pixel space, which log_prob()'s 'log_prob' (with its log_jac term) describes.
+
+        Returns a dict: 'x' [B,H,W,x_d], the last iterate in the space of x; 'log_prob' [steps+1,B], row t the
+        flow-input-space log-density of iterate t (row 0: the start, the last row: 'x'); with return_state
+        'state' = {'m', 'v' [B,H,W,x_d], 'step'}, Adam's moments and the steps taken, which passed back as
+        state= continues the run: ascend(steps=a) then ascend(steps=b, state=...) from its 'x' equals
+        ascend(steps=a + b) bit for bit when no transform is applied between them. The images run `chunk` at a
+        time (default min(B, 64)); rows of 'log_prob' and iterates agree across chunk up to fp32 rounding (see
+        score). An image with an element outside the logit map's domain keeps x and has -inf in every row."""
+        x, y = self._paired_xy(x, y, 'cFlow.ascend')
+        B = int(x.shape[0])
+        steps = int(steps)
+        if chunk is None:
+            chunk = max(1, min(B, 64))
+        first = 0
+        m = v = None
+        if state is not None:
+            m, v, first = _as_input(state['m'], "state['m']"), _as_input(state['v'], "state['v']"), int(state['step'])
+            if tuple(m.shape) != tuple(x.shape) or tuple(v.shape) != tuple(x.shape):
+                raise ValueError(f"state['m'] and state['v'] must have x's shape {tuple(x.shape)}")
+            m, v = m.clone(), v.clone()   # (the call updates them in place: the caller's state stays valid)
+        elif return_state:
+            m, v = torch.zeros_like(x), torch.zeros_like(x)
+        desc = _lib.cnf_ascend_desc(int(chunk), steps, float(lr), float(beta_1), float(beta_2), float(epsilon),
+                                    float(logit_a or 0.0), int(bool(residual)), first)
+        lib = _lib.load()
+        ws = _call_workspace(self._ws, ('ascend', int(chunk)), self.device, 'cFlow.ascend',
+                             lambda: lib.cnf_plan_ascend_workspace_bytes(self._plan, B, C.byref(desc)))
+        out = {'x': torch.empty_like(x),
+               'log_prob': torch.empty((max(steps, 0) + 1, B), device=x.device, dtype=torch.float32)}
+        check(lib.cnf_flow_ascend(self._plan, ptr(self.params), ptr(self._aux), ptr(x), ptr(y), C.byref(desc),
+                                  ptr(out['x']), ptr(out['log_prob']), ptr(m), ptr(v), ptr(ws), B, _stream()),
+              'cnf_flow_ascend')
+        if return_state:
+            out['state'] = {'m': m, 'v': v, 'step': first + steps}
+        return out
+
     # -- loss -----------------------------------------------------------------------------------
     def nll_sums(self, xy, zy=None, logdet_per_image=None):
         """Per-batch sums of the NLL terms on device: (sum loss_i, sum -llz_i, sum -lly_i,

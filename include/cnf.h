@@ -380,6 +380,72 @@ int cnf_flow_log_prob(cnf_plan* plan, const float* params, const float* aux, con
                       float* logdet, float* log_jac, float* y_dev, const float* log_prior,
                       float* posterior, float* log_evidence, void* workspace, int B, void* stream);
 
+/* The input gradients of the log-density: grad_x [B][H][W][x_d] = d log_prob[b] / d x[b] and grad_y
+ * [B][H][W][D-x_d] = d log_prob[b] / d y[b] of cnf_flow_log_prob's paired log_prob = llz + logdet + log_jac
+ * (image b under condition b), with x and y as that call takes them (x in the space of the samples; the
+ * condition enters through the y channels of the flow's input and, with residual, through x - y).
+ * Per chunk: cnf_flow_log_prob's gather, cnf_flow_forward_train's schedule, the seed d(llz + logdet)/dzy
+ * (k_score_seed: -z on the x channels, 0 elsewhere, log-det weight +1), the training backward restricted to
+ * the data gradients -- no launch whose only outputs are parameter gradients, no dparams -- and k_score_finish,
+ * which takes the flow-input gradient g through the gather's map: with v = x - y (residual) or x and
+ * e = a + c1 v, t = g_x c1 / (span e (1 - e)) - c1 (1 - 2e) / (e (1 - e)) (t = g_x without logit_a);
+ * grad_x = t, grad_y = g_y (- t with residual). log_prob [B] is cnf_flow_log_prob's value up to the rounding
+ * of the training forward's schedule. Any of the three outputs may be NULL, not all; with grad_x and grad_y
+ * NULL no backward runs. An image with an element outside the logit map's domain gets log_prob = -inf and NaN
+ * gradients; the other images are untouched. log_prob does not depend on chunk bit for bit; the gradients
+ * agree across chunk up to fp32 rounding (k_tconv_band's tile height, and with it the number of partials of
+ * the fused LayerNorm-backward reduction per image, follows the launch's workgroup count, which counts the
+ * chunk's images). */
+typedef struct cnf_score_desc {
+    int   chunk;          /* images per forward / backward, >= 1 */
+    float logit_a;        /* as cnf_logp_desc */
+    int   residual;
+} cnf_score_desc;
+
+/* Workspace bytes of cnf_flow_score: cnf_plan_train_workspace_bytes(desc->chunk), the dense backward image
+ * (packed once per call), one chunk each of xy, zy, the seed, the per-image log-det, the log_jac partials and
+ * llz; independent of B. 0, with the reason in cnf_last_error, for a NULL or invalid argument. */
+size_t cnf_plan_score_workspace_bytes(const cnf_plan* plan, int B, const cnf_score_desc* desc);
+
+/* CNF_E_INVALID before any HIP call, with "cnf_flow_score: " and the reason in cnf_last_error, for: a NULL
+ * plan, params, aux, workspace, x or y; all of grad_x, grad_y, log_prob NULL; a NULL desc; B < 1; chunk < 1;
+ * logit_a outside {0} u (0, 0.5); residual with D - x_d != x_d. Not capturable into a graph when a streamed
+ * layer's backward forks onto the plan's side stream. */
+int cnf_flow_score(cnf_plan* plan, const float* params, const float* aux, const float* x, const float* y,
+                   const cnf_score_desc* desc, float* grad_x, float* grad_y, float* log_prob,
+                   void* workspace, int B, void* stream);
+
+/* Gradient ascent on the flow-input-space log-density llz + logdet (what cnf_flow_sample_logp reports for a
+ * draw) over the x channels of the flow's input, y fixed. Per chunk: x0 is gathered into flow space as above
+ * (u0 = logit_value(x0 - y)); `steps` times the training forward, the seed, the data-gradient backward and
+ * k_ascend_step -- Keras Adam (cnf_adam_step's arithmetic) with the gradient -g, written in place into the xy
+ * the next forward reads; one last forward; x_out [B][H][W][x_d] = the iterate through the sampler's
+ * post-transform (de_logitify, + y). log_prob_trace [steps+1][B]: row t = llz + logdet of iterate t, row 0 the
+ * start, row `steps` what x_out holds. No host synchronisation between steps. m, v [B][H][W][x_d] (both or
+ * neither): Adam's moments, read and written, so that a run continues with first_step = the steps taken so far
+ * (the step counter starts at first_step + 1); NULL: the state lives in the workspace and starts at zero.
+ * The mode of a density depends on the parametrisation: with logit_a this is the mode in flow-input space,
+ * not in pixel space. An image with an element outside the logit map's domain gets -inf in every trace row
+ * and x_out = x0. */
+typedef struct cnf_ascend_desc {
+    int   chunk, steps;   /* images per forward / backward, >= 1; ascent steps, >= 0 */
+    float lr, beta_1, beta_2, epsilon;   /* Adam: lr finite, betas in [0, 1), epsilon >= 0 */
+    float logit_a;        /* as cnf_logp_desc */
+    int   residual;
+    int   first_step;     /* Adam steps already taken on m, v; >= 0 */
+} cnf_ascend_desc;
+
+/* Workspace bytes of cnf_flow_ascend: cnf_flow_score's plus one chunk of m and v; independent of B. */
+size_t cnf_plan_ascend_workspace_bytes(const cnf_plan* plan, int B, const cnf_ascend_desc* desc);
+
+/* CNF_E_INVALID before any HIP call, with "cnf_flow_ascend: " and the reason in cnf_last_error, for: a NULL
+ * plan, params, aux, workspace, x0, y, x_out or log_prob_trace; one of m, v without the other; a NULL desc;
+ * B < 1; chunk < 1; steps < 0; first_step < 0; lr not finite; a beta outside [0, 1); epsilon negative or not
+ * finite; logit_a outside {0} u (0, 0.5); residual with D - x_d != x_d. x_out may be x0. */
+int cnf_flow_ascend(cnf_plan* plan, const float* params, const float* aux, const float* x0, const float* y,
+                    const cnf_ascend_desc* desc, float* x_out, float* log_prob_trace, float* m, float* v,
+                    void* workspace, int B, void* stream);
+
 /* coupling_layer.forward_and_Jacobian (:1258-1328) for layer `layer` of
  * layers_list: u -> v (shape of the layer's in_shape); logdet_accum[B] +=
  * per-image sum of A(u1) (pass NULL to skip). u and v must not alias. */
