@@ -11,8 +11,8 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / 'csrc'
 # CNF_BUILD_LIB: write a diagnostic build elsewhere (e.g. the host-sanitizer build, tools/host_sanitize.sh)
 LIB = Path(os.environ['CNF_BUILD_LIB']) if os.environ.get('CNF_BUILD_LIB') else PKG / 'lib' / 'libcnf_hip.so'
-SOURCES = ['cnf_kernels.hip', 'cnf_stream.hip', 'cnf_netlds.hip', 'cnf_toy.hip', 'cnf_toy_train.hip', 'cnf_toy_sample.hip', 'cnf_toy_density.hip', 'cnf_train.hip', 'cnf_ldsbwd.hip', 'cnf_transforms.hip', 'cnf_sample.hip', 'cnf_logprob.hip', 'cnf_score.hip', 'cnf_runtime.cpp', 'cnf_coupling.cpp',
-           'cnf_plan.cpp', 'cnf_train.cpp', 'cnf_comm.cpp', 'cnf_schedule.cpp', 'cnf_sampling.cpp', 'cnf_cascade.cpp', 'cnf_logprob.cpp', 'cnf_score.cpp', 'cnf_toy_api.cpp', 'cnf_debug.cpp']
+SOURCES = ['cnf_kernels.hip', 'cnf_stream.hip', 'cnf_netlds.hip', 'cnf_toy.hip', 'cnf_toy_train.hip', 'cnf_toy_sample.hip', 'cnf_toy_density.hip', 'cnf_train.hip', 'cnf_ldsbwd.hip', 'cnf_transforms.hip', 'cnf_sample.hip', 'cnf_logprob.hip', 'cnf_score.hip', 'cnf_optim.hip', 'cnf_runtime.cpp', 'cnf_coupling.cpp',
+           'cnf_plan.cpp', 'cnf_train.cpp', 'cnf_comm.cpp', 'cnf_schedule.cpp', 'cnf_sampling.cpp', 'cnf_cascade.cpp', 'cnf_logprob.cpp', 'cnf_score.cpp', 'cnf_optim.cpp', 'cnf_toy_api.cpp', 'cnf_debug.cpp']
 HEADERS = ["cnf_kernels.h", "cnf_device.h", "cnf_toy_device.h", "cnf_plan.h", "cnf_api.h", "cnf_sampling.h", "cnf_netlds_shapes.inc", "cnf_gc_shapes.inc", "cnf_pw_shapes.inc"]
 ARCH = os.environ.get('CNF_OFFLOAD_ARCH', 'gfx950')
 

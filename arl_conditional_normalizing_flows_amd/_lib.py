@@ -71,6 +71,15 @@ class cnf_ascend_desc(C.Structure):
                 ('first_step', C.c_int)]
 
 
+class cnf_optim_desc(C.Structure):
+    _fields_ = [('lr', C.c_float), ('beta_1', C.c_float), ('beta_2', C.c_float), ('epsilon', C.c_float),
+                ('clipvalue', C.c_float), ('clipnorm', C.c_float), ('global_clipnorm', C.c_float),
+                ('skip_nonfinite', C.c_int), ('ema_momentum', C.c_float)]
+
+
+OPTIM_STATS_FLOATS = 8   # CNF_OPTIM_STATS_FLOATS
+
+
 class cnf_toy_sample_desc(C.Structure):
     _fields_ = [('num_samples', C.c_int), ('temperature', C.c_float), ('seed', C.c_uint64), ('offset', C.c_uint64),
                 ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
@@ -134,6 +143,13 @@ _SIGS = [
     ('cnf_coupling_backward', C.c_int, [_P, C.c_int, _F, _F, _F, _F, C.c_float, _P, C.c_int, _F, _P]),
     ('cnf_adam_step', C.c_int, [_F, _F, _F, _F, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                 _P]),
+    ('cnf_optim_slab_elems', C.c_int, []),
+    ('cnf_optim_num_slabs', C.c_int64, [C.c_int64, C.POINTER(C.c_int64), C.c_int]),
+    ('cnf_optim_table_bytes', C.c_size_t, [C.c_int64, C.POINTER(C.c_int64), C.c_int]),
+    ('cnf_optim_table_build', C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.c_int, _P]),
+    ('cnf_optim_workspace_bytes', C.c_size_t, [C.c_int64, C.c_int, C.c_int64]),
+    ('cnf_optim_step', C.c_int, [_F, _F, _F, _F, _F, C.c_int64, _P, C.c_int64, C.c_int, C.POINTER(cnf_optim_desc),
+                                 _P, _F, _F, _P, _P]),
     ('cnf_toy_num_params', C.c_int64, [C.POINTER(cnf_toy_desc)]),
     ('cnf_toy_call', C.c_int, [C.POINTER(cnf_toy_desc), _F, _F, _F, _F, _F, C.c_int, C.c_int, _P]),
     ('cnf_toy_nll_sums', C.c_int, [_F, _F, C.c_int, _P]),

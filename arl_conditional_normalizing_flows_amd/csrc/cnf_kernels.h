@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "../../include/cnf.h"   // cnf_optim_desc
+
 namespace cnf {
 
 constexpr float LRELU_ALPHA = 0.3f;      // keras.layers.LeakyReLU() default
@@ -1000,4 +1002,44 @@ void launch_nll_grad(const float* xy, const float* zy, float* dzy, int B, int HW
                      float inv_batch, const float* count, hipStream_t st);
 void launch_adam(float* params, const float* grads, float* m, float* v, long long n, float alpha, float b1, float b2,
                  float eps, hipStream_t st);
+
+// Clipped, guarded Adam (cnf_optim.hip; the rules: include/cnf.h at cnf_optim_step). One slab of the table:
+// elements [start, start + count) of tensor `tensor`, count <= OPTIM_SLAB, never across a tensor boundary.
+constexpr int OPTIM_SLAB = 4096;
+struct OptimSlab {
+    long long start;
+    int count, tensor;
+};
+// The step's workspace: per-slab sums and counts, the tensors' scales, then the control record.
+struct OptimCtrl {
+    float alpha;   // the step size of this step
+    int skip;      // non-zero: k_optim_step writes nothing
+};
+struct OptimWs {
+    double* sum_g;       // [num_slabs] sum of g^2
+    double* sum_h;       // [num_slabs] sum of h^2 (h = clamped g)
+    unsigned* nonfinite; // [num_slabs] elements of g that are NaN or +-inf
+    float* scale;        // [T] s_t after k_optim_finish's first pass, scale_t = fl32(s_t * S) after its second
+    OptimCtrl* ctrl;
+    size_t total;        // bytes
+};
+OptimWs optim_ws(void* base, int T, long long num_slabs);
+struct OptimArgs {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* ema;               // null without EMA
+    const OptimSlab* slabs;   // [num_slabs], device
+    const int* first;         // [T + 1], device: tensor t's slabs are first[t] .. first[t + 1] - 1
+    long long num_slabs;
+    int T;
+    bool vec;                 // p, g, m, v, ema are all 16-byte aligned (else every access is scalar)
+    cnf_optim_desc d;
+    long long* state;         // [0] applied, [1] skipped
+    float* stats;             // [CNF_OPTIM_STATS_FLOATS] or null
+    float* scales_out;        // [T] or null
+    OptimWs ws;
+};
+void launch_optim(const OptimArgs& a, hipStream_t st);   // k_optim_stats, k_optim_finish, k_optim_step
 }  // namespace cnf

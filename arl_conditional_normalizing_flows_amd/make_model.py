@@ -916,6 +916,8 @@ class cFlow:
         """keras Model.compile(optimizer=Adam(...)) (conv_cINN.py:567-569)."""
         from .optimizers import Adam
         self.optimizer = optimizer if optimizer is not None else Adam()
+        if hasattr(self.optimizer, 'bind'):   # the tensor table of the per-tensor clipping (optimizers.Adam.bind)
+            self.optimizer.bind([o for _, o, _ in self.param_specs] + [self.num_params], self.device)
 
     def _train_workspace(self, B):
         key = ('train', B)

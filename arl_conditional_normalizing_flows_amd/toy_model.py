@@ -318,6 +318,11 @@ class cINN_affine:
         """keras Model.compile(optimizer=Adam(1e-4)) (TOYcINN.py:213-304)."""
         from .optimizers import Adam
         self.optimizer = optimizer if optimizer is not None else Adam()
+        if hasattr(self.optimizer, 'bind'):   # the tensor table of the per-tensor clipping (optimizers.Adam.bind)
+            offsets = [0]
+            for _, s in self.param_specs():
+                offsets.append(offsets[-1] + int(np.prod(s)))
+            self.optimizer.bind(offsets, self.device)
 
     def _train_workspace(self, B):
         """(training workspace, flat gradient buffer), cached per B."""

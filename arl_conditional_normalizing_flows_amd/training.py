@@ -12,6 +12,8 @@ the annealed instance-noise schedule, over the HIP train_step / test_step.
   anneal_and_fit(...)            conv_cINN.py:583-636: num_annealing_epochs one-epoch fits on
                                  instance_noise(xy, alpha = i / num_annealing_epochs), then the
                                  clean fit up to num_epochs
+  ema_weights(model)             context manager: evaluate with the optimizer's weight average
+                                 (Adam(use_ema=True)), the training weights restored on exit
   save_weights / load_weights    Keras-layout .h5 (keras_h5.py) or {canonical name: array} .npz
                                  (np.load with allow_pickle=False)
 
@@ -20,6 +22,7 @@ re-invoked each epoch (the tf.data re-iteration of the reference).
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import math
 import os
@@ -55,6 +58,24 @@ def load_weights(model, path):
         return
     with np.load(path, allow_pickle=False) as z:
         model.set_weights({k: z[k] for k in z.files})
+
+
+@contextlib.contextmanager
+def ema_weights(model):
+    """Evaluate with the optimizer's weight average (Adam(use_ema=True), Keras' use_ema / ema_momentum):
+    inside the context model.params holds the EMA vector -- put in through model.set_weights, which
+    repacks cFlow's kernel-side weights (cnf_pack_params); the toy model's kernels read params directly --
+    and on exit the training weights are back, bit for bit. Do not train inside the context."""
+    ema = getattr(getattr(model, 'optimizer', None), 'ema', None)
+    if ema is None:
+        raise RuntimeError('ema_weights: the model has no EMA yet: compile it with Adam(use_ema=True) and take a '
+                           'training step first')
+    keep = model.params.detach().clone()
+    model.set_weights(ema)
+    try:
+        yield model
+    finally:
+        model.set_weights(keep)
 
 
 class Callback:

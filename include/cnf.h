@@ -541,6 +541,79 @@ int cnf_coupling_backward(cnf_plan* plan, int layer, const float* params, const 
 int cnf_adam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr,
                   float beta_1, float beta_2, float epsilon, int step, void* stream);
 
+/* ---- Clipped, guarded Adam (tf.keras.optimizers.Adam's clipvalue / clipnorm / global_clipnorm and
+ * use_ema / ema_momentum, plus a skip of steps whose gradient holds a NaN or an infinity). The step
+ * size's t is a counter on the device and nothing in the step reads the device from the host, so a
+ * graph-captured cnf_optim_step advances on every replay. cnf_adam_step is not changed by any of this.
+ *
+ * A "tensor" is a range [offsets[t], offsets[t + 1]) of the flat parameter vector (offsets[T + 1]:
+ * non-decreasing, offsets[0] = 0, offsets[T] = n; an empty tensor is allowed). With the gradient g:
+ *   1. clipvalue c > 0: h = min(max(g, -c), c); otherwise h = g
+ *   2. clipnorm c > 0, per tensor: n_t = sqrt(sum_t h^2) (fp64 sum of the fp32 values),
+ *      s_t = (float)(c / max(n_t, c)) (1 for a zero or empty tensor); otherwise s_t = 1
+ *   3. global_clipnorm c > 0: N = sqrt(sum_t (double)s_t^2 * sum_t h^2), S = (float)(c / max(N, c));
+ *      otherwise S = 1 (N is computed and reported either way)
+ *   4. g' = fl32(h * scale_t), scale_t = fl32(s_t * S): rounded to fp32 before Adam uses it
+ *   5. cnf_adam_step's arithmetic on g' with t = applied + 1 and
+ *      alpha = (float)(lr sqrt(1 - beta_2^t) / (1 - beta_1^t)) taken on the device in fp64
+ *   6. ema_momentum > 0: ema += (p' - ema) * (1 - ema_momentum), in the same pass as the update
+ *   7. skip_nonfinite and any element of g NaN or +-inf: params, m, v and ema are not written,
+ *      applied stays and skipped increments (the next good step uses the t this one would have).
+ *      Without skip_nonfinite such values propagate as IEEE arithmetic gives.
+ * Every sum is taken in a fixed order without atomics (per slab in fp64, a tensor's slabs in slab
+ * order, the tensors in table order): results are bitwise repeatable and do not depend on what the
+ * workspace held before. */
+typedef struct cnf_optim_desc {
+    float lr, beta_1, beta_2, epsilon;   /* lr finite, betas in [0, 1), epsilon >= 0 */
+    float clipvalue;                     /* 0 = off; else > 0 and finite */
+    float clipnorm;                      /* 0 = off; not together with global_clipnorm */
+    float global_clipnorm;               /* 0 = off */
+    int   skip_nonfinite;                /* non-zero: rule 7 */
+    float ema_momentum;                  /* 0 = no EMA; else in (0, 1), and ema must be given */
+} cnf_optim_desc;
+
+/* Elements per slab, the unit of work of the three kernels (a multiple of 4). */
+int cnf_optim_slab_elems(void);
+
+/* Number of slabs of the table of (n, offsets, T): the sum over tensors of
+ * ceil(size_t / cnf_optim_slab_elems()), no slab crossing a tensor boundary. -1 for an invalid
+ * argument (n < 1, T < 1, NULL, offsets not non-decreasing from 0 to n). */
+int64_t cnf_optim_num_slabs(int64_t n, const int64_t* offsets, int T);
+
+/* Bytes of that table (0 for an invalid argument): num_slabs entries
+ * {int64 start, int32 count, int32 tensor} in order of start, then int32 first[T + 1], tensor t's
+ * slabs being first[t] .. first[t + 1] - 1. */
+size_t cnf_optim_table_bytes(int64_t n, const int64_t* offsets, int T);
+
+/* Writes the table to host_out (cnf_optim_table_bytes bytes). Host code only: the caller copies
+ * it to the device once and passes that copy as table_dev to every step. */
+int cnf_optim_table_build(int64_t n, const int64_t* offsets, int T, void* host_out);
+
+/* Bytes of cnf_optim_step's workspace (per-slab sums and counts, the tensors' scales, alpha and the
+ * skip flag); 0 for an invalid argument. Every byte the step reads it has written in the same call. */
+size_t cnf_optim_workspace_bytes(int64_t n, int T, int64_t num_slabs);
+
+#define CNF_OPTIM_STATS_FLOATS 8
+/* One step, three launches on `stream`: k_optim_stats (per slab: fp64 sums of g^2 and h^2, the count
+ * of non-finite g), k_optim_finish (one workgroup: s_t, N, S, scale_t, skip, the counters, alpha,
+ * stats), k_optim_step (clamp, scale, Adam, EMA over the slabs; returns at once on a skipped step).
+ *   params, grads, m, v [n]; ema [n] or NULL (required when ema_momentum > 0; the caller sets it to
+ *       the parameters before the first step)
+ *   table_dev: the device copy of cnf_optim_table_build's table for this (n, offsets, T)
+ *   state_dev int64[2]: [0] steps applied, [1] steps skipped; the caller zeroes it once
+ *   stats_dev float[CNF_OPTIM_STATS_FLOATS] or NULL: [0] the global norm of g, [1] N of rule 3,
+ *       [2] the number of non-finite elements of g, [3] 1 if this step was skipped else 0, [4] alpha,
+ *       [5] S, [6..7] 0
+ *   scales_dev float[T] or NULL: scale_t of rule 4
+ * CNF_E_INVALID before anything is launched ("cnf_optim_step: ..." in cnf_last_error) for a NULL
+ * required pointer, n < 1, T < 1, num_slabs < 1, a negative or non-finite clip value, clipnorm
+ * together with global_clipnorm, a beta outside [0, 1), a negative epsilon, a non-finite lr, an
+ * ema_momentum outside [0, 1), ema_momentum > 0 with ema NULL. (Bad offsets are refused where they
+ * are given: cnf_optim_num_slabs / _table_bytes / _table_build.) */
+int cnf_optim_step(float* params, const float* grads, float* m, float* v, float* ema, int64_t n,
+                   const void* table_dev, int64_t num_slabs, int T, const cnf_optim_desc* desc,
+                   int64_t* state_dev, float* stats_dev, float* scales_dev, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------
  * TOYcINN (BASELINE configs[0]): the dense conditional flow of
  * TOYcINN_make_model.py:29-506 on 3-dimensional points.
