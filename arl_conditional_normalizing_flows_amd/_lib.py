@@ -80,6 +80,16 @@ class cnf_optim_desc(C.Structure):
 OPTIM_STATS_FLOATS = 8   # CNF_OPTIM_STATS_FLOATS
 
 
+class cnf_batch_desc(C.Structure):
+    _fields_ = [('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('mode', C.c_int), ('logit_a', C.c_float),
+                ('x_down', C.c_int), ('y_levels', C.c_int), ('residual', C.c_int),
+                ('alpha0', C.c_float), ('seed0', C.c_uint64), ('offset0', C.c_uint64),
+                ('alpha1', C.c_float), ('seed1', C.c_uint64), ('offset1', C.c_uint64)]
+
+
+BATCH_CLASS, BATCH_SR = 0, 1   # CNF_BATCH_CLASS, CNF_BATCH_SR
+
+
 class cnf_toy_sample_desc(C.Structure):
     _fields_ = [('num_samples', C.c_int), ('temperature', C.c_float), ('seed', C.c_uint64), ('offset', C.c_uint64),
                 ('hist_bins', C.c_int), ('hist_lo', C.c_float * 2), ('hist_hi', C.c_float * 2)]
@@ -168,6 +178,7 @@ _SIGS = [
     ('cnf_down', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_up', C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('cnf_instance_noise', C.c_int, [_F, _F, C.c_int64, C.c_float, C.c_uint64, C.c_uint64, _P]),
+    ('cnf_batch_assemble', C.c_int, [_F, C.c_int64, _P, _F, C.POINTER(cnf_batch_desc), _F, C.c_int, _P]),
     ('cnf_plan_num_recorded_launches', C.c_int, [_P]),
     ('cnf_plan_recorded_launch_info', C.c_int, [_P, C.c_int, C.c_char_p, C.c_int,
                                                 C.POINTER(C.c_double), C.POINTER(C.c_double)]),

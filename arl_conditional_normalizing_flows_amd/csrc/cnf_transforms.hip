@@ -119,6 +119,65 @@ __global__ __launch_bounds__(256) void k_prep(float* __restrict__ out, long long
         out[i] = input_prep_value(q.src[i], (int)(i % q.D), q, q.off + (uint64_t)i);
 }
 
+// cnf_batch_assemble: one training batch from the cached images in one pass. Element e of the output
+// (batch-major NHWC) is k_logit / the label plane (CLASS) or k_sr (SR) of image index[b], then up to two
+// k_noise stages of stream elements offset + e, in the same device functions as those kernels, so the
+// result is theirs bit for bit. An index outside [0, N) is never dereferenced: its image is all NaN.
+struct BatchArgs {
+    const float* images;
+    const int64_t* index;
+    const float* label;
+    long long N;
+    int H, W, C, sr, logit, xd, yl, residual;
+    LogitK lk;
+    int on0, on1;   // a stage with alpha 1 is skipped, not computed: fmaf(1, x, 0 z) is x only for a finite z
+    float alpha0, alpha1;
+    uint64_t seed0, off0, seed1, off1;
+};
+
+__global__ __launch_bounds__(256) void k_batch(BatchArgs a, float* __restrict__ xy, long long n) {
+    const int Ho = a.H >> a.xd, Wo = a.W >> a.xd;
+    const int D = a.sr ? 2 * a.C : a.C + 1;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const int ch = (int)(e % D);
+        const long long p = e / D;
+        const int j = (int)(p % Wo);
+        const long long q = p / Wo;
+        const int i = (int)(q % Ho);
+        const int b = (int)(q / Ho);
+        const long long idx = a.index[b];
+        if (idx < 0 || idx >= a.N) {
+            xy[e] = __builtin_nanf("");
+            continue;
+        }
+        const float* img = a.images + (size_t)idx * a.H * a.W * a.C;
+        float v;
+        if (!a.sr) {
+            if (ch < a.C) {
+                v = img[((size_t)i * a.W + j) * a.C + ch];
+                if (a.logit) v = logit_value(v, a.lk);
+            } else {
+                v = a.label[b];
+            }
+        } else {   // k_sr's x and y of channel c
+            const int c = ch < a.C ? ch : ch - a.C;
+            const int s = 1 << a.xd;
+            const int m = 1 << a.yl;
+            const int bi = (i / m) * m, bj = (j / m) * m;
+            const float y = nested_mean(img, a.W, a.C, bi * s, bj * s, c, a.xd + a.yl);
+            if (ch < a.C) {
+                const float x0 = nested_mean(img, a.W, a.C, i * s, j * s, c, a.xd);
+                v = a.residual ? x0 - y : x0;
+            } else {
+                v = y;
+            }
+        }
+        if (a.on0) v = instance_noise_value(v, true, a.alpha0, a.seed0, a.off0 + (uint64_t)e);
+        if (a.on1) v = instance_noise_value(v, true, a.alpha1, a.seed1, a.off1 + (uint64_t)e);
+        xy[e] = v;
+    }
+}
+
 int grid_for(long long n) {
     long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
@@ -183,6 +242,56 @@ int cnf_instance_noise(const float* x, float* out, int64_t n, float alpha, uint6
     hipLaunchKernelGGL(cnf::k_noise, dim3(cnf::grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, out, (long long)n,
                        alpha, seed, offset);
     return cnf::finish("k_noise");
+}
+
+int cnf_batch_assemble(const float* images, int64_t N, const int64_t* index_dev, const float* label_dev,
+                       const cnf_batch_desc* desc, float* xy, int B, void* stream) {
+    auto bad = [](const char* why) {
+        return cnf::set_error(CNF_E_INVALID, (std::string("cnf_batch_assemble: ") + why).c_str());
+    };
+    if (!images || !index_dev || !desc || !xy) return bad("null images, index_dev, desc or xy");
+    if (B < 1 || N < 1) return bad("B and N must be >= 1");
+    const cnf_batch_desc& d = *desc;
+    if (d.H <= 0 || d.W <= 0 || d.C <= 0) return bad("H, W and C must be positive");
+    if (d.mode != CNF_BATCH_CLASS && d.mode != CNF_BATCH_SR) return bad("unknown mode");
+    const bool sr = d.mode == CNF_BATCH_SR;
+    if (!sr && !label_dev) return bad("CLASS mode needs label_dev");
+    if (sr && label_dev) return bad("SR mode takes no label_dev");
+    if (!(d.logit_a == 0.f || (d.logit_a > 0.f && d.logit_a < 0.5f))) return bad("logit_a must be 0 or in (0, 0.5)");
+    if (sr && d.logit_a != 0.f) return bad("logit_a is for CLASS mode only");
+    if (sr) {
+        if (d.x_down < 0 || d.y_levels < 0 || d.x_down + d.y_levels > 8) return bad("bad SR levels");
+        const int m = 1 << (d.x_down + d.y_levels);
+        if (d.H % m || d.W % m) return bad("H and W must be divisible by 2^(x_down + y_levels)");
+    }
+    for (float al : {d.alpha0, d.alpha1})
+        if (!std::isfinite(al) || al < 0.f || al > 1.f) return bad("alpha0 and alpha1 must be finite and in [0, 1]");
+    cnf::BatchArgs a{};
+    a.images = images;
+    a.index = index_dev;
+    a.label = label_dev;
+    a.N = (long long)N;
+    a.H = d.H;
+    a.W = d.W;
+    a.C = d.C;
+    a.sr = sr;
+    a.logit = d.logit_a != 0.f;
+    if (a.logit) a.lk = cnf::logit_consts(d.logit_a);
+    a.xd = sr ? d.x_down : 0;
+    a.yl = sr ? d.y_levels : 0;
+    a.residual = sr && d.residual;
+    a.on0 = d.alpha0 != 1.f;
+    a.on1 = d.alpha1 != 1.f;
+    a.alpha0 = d.alpha0;
+    a.alpha1 = d.alpha1;
+    a.seed0 = d.seed0;
+    a.off0 = d.offset0;
+    a.seed1 = d.seed1;
+    a.off1 = d.offset1;
+    const long long n = sr ? (long long)B * (d.H >> d.x_down) * (d.W >> d.x_down) * 2 * d.C
+                           : (long long)B * d.H * d.W * (d.C + 1);
+    hipLaunchKernelGGL(cnf::k_batch, dim3(cnf::grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, xy, n);
+    return cnf::finish("k_batch");
 }
 
 }  // extern "C"

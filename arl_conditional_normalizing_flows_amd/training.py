@@ -18,7 +18,8 @@ the annealed instance-noise schedule, over the HIP train_step / test_step.
                                  (np.load with allow_pickle=False)
 
 Datasets are iterables of device batches (torch tensors [B, H, W, D]); `callable` datasets are
-re-invoked each epoch (the tf.data re-iteration of the reference).
+re-invoked each epoch (the tf.data re-iteration of the reference). datasets.py has the image
+pipelines in that form; anneal_and_fit lets such a dataset add the annealing noise itself (with_noise).
 """
 from __future__ import annotations
 
@@ -345,7 +346,9 @@ def anneal_and_fit(model, xy_train: Iterable, xy_val: Optional[Iterable], num_an
     redrawn every epoch (counter offsets advance per batch). As in the reference, each fit()
     starts with stop_training reset (keras), so an EarlyStopping that fires during annealing
     ends that one-epoch fit only and the schedule carries on. process_group: see fit (each rank
-    passes its own shard; the noise is seeded per rank so shards draw independent noise)."""
+    passes its own shard; the noise is seeded per rank so shards draw independent noise). A dataset
+    with a with_noise method (datasets.py) adds the noise in its own batch-assembly launch, with the
+    same seeds and offsets: the same batches, bit for bit."""
     completed = 0
     hist = None
     rank = _rank(process_group)
@@ -355,6 +358,11 @@ def anneal_and_fit(model, xy_train: Iterable, xy_val: Optional[Iterable], num_an
             print(f'Annealing instance noise, alpha={alpha}, annealing epoch {i} of {num_annealing_epochs}.')
 
         def noisy(data, tag):
+            if hasattr(data, 'with_noise'):
+                # a device-resident dataset (datasets.py) adds this noise in its own batch-assembly launch:
+                # the same seed and offsets, so the same batches bit for bit
+                return data.with_noise(alpha, seed * 1000003 + 7919 * i + tag + 104729 * rank, offset=0)
+
             def gen():
                 off = 0
                 for xy in _batches(data):

@@ -804,6 +804,44 @@ int cnf_up(const float* in, float* out, int B, int H, int W, int C, void* stream
 int cnf_instance_noise(const float* x, float* out, int64_t n, float alpha, uint64_t seed, uint64_t offset,
                        void* stream);
 
+/* One training batch from a device-resident image cache in one launch (the per-batch half of the
+ * reference's input pipeline, conv_cINN.py:209-508: gather, preprocess, label plane, the 2 %
+ * baseline noise and the annealing noise). images [N][H][W][C] fp32 in [0, 1]; index_dev [B] picks
+ * the batch's images. xy is [B][H][W][C+1] (CLASS) or [B][H>>x_down][W>>x_down][2C] (SR). For flat
+ * element e of the whole xy tensor (batch-major NHWC), image b:
+ *   v0  CLASS: channels < C: the pixel of images[index[b]], through cnf_logit's forward map if
+ *              logit_a; channel C: label_dev[b]
+ *       SR:    cnf_sr_preprocess's x and y of images[index[b]] (the same nested 2x2 means, x0 - y
+ *              when residual)
+ *   v1  = alpha0 v0 + (1 - alpha0) N(0,1) of stream element (seed0, offset0 + e); v0 if alpha0 == 1
+ *   v2  = the same with (alpha1, seed1, offset1) on v1;                           v1 if alpha1 == 1
+ *   xy[e] = v2
+ * Contract: xy equals, bit for bit, this composition of calls on the gathered images:
+ * cnf_logit (CLASS, if logit_a) or cnf_sr_preprocess (SR), the label plane concatenated (CLASS),
+ * cnf_instance_noise(., n, alpha0, seed0, offset0), cnf_instance_noise(., n, alpha1, seed1,
+ * offset1) -- the kernels share their device functions. A stage whose alpha is 1 is skipped, not
+ * computed (alpha x + 0 z is x only for a finite z).
+ * An index[b] outside [0, N) is never dereferenced: every element of that image is NaN. The guard
+ * is in the kernel; the host never reads index_dev or label_dev.
+ * CNF_E_INVALID ("cnf_batch_assemble: ..."), before any HIP call: a NULL images, index_dev, desc
+ * or xy; B < 1 or N < 1; H, W or C <= 0; an unknown mode; CLASS without label_dev or SR with one;
+ * logit_a outside {0} U (0, 0.5), or given in SR mode; SR levels cnf_sr_preprocess refuses; an
+ * alpha that is not finite or outside [0, 1]. */
+#define CNF_BATCH_CLASS 0
+#define CNF_BATCH_SR    1
+typedef struct cnf_batch_desc {
+    int H, W, C;            /* the cached images [N][H][W][C], fp32 in [0,1] */
+    int mode;               /* CNF_BATCH_CLASS | CNF_BATCH_SR */
+    float logit_a;          /* CLASS: 0 = raw pixels, else in (0, 0.5): preprocess_dataset_class(LOGITS=True, a) on x */
+    int x_down, y_levels, residual;   /* SR: cnf_sr_preprocess's arguments */
+    float alpha0; uint64_t seed0, offset0;   /* noise stage 0 (the 2 % baseline); alpha0 == 1: stage off */
+    float alpha1; uint64_t seed1, offset1;   /* noise stage 1 (annealing), applied to stage 0's result; 1: off */
+} cnf_batch_desc;
+
+int cnf_batch_assemble(const float* images, int64_t N, const int64_t* index_dev /* [B] */,
+                       const float* label_dev /* [B]; CLASS only, else NULL */,
+                       const cnf_batch_desc* desc, float* xy, int B, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange: one process per GPU, the batch
  * sharded over ranks, ONE all-reduce of the NLL sums. Replaces the batch means
